@@ -2,10 +2,18 @@
 """
 bench.py -- throughput of the MI355X render path on the BASELINE.json configurations.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c1|c3|c4|c5|supersaw]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c1|c3|c4|c5|supersaw] [--full]
+                    [--dump-outputs DIR]
 
 Prints ONE JSON line (rank 0).  Metric: Msamples/s = output frames rendered per wall second x 1e-6, the
 metric of the reference's benchmarks/benchmark_pes.py:62-66.
+
+A plain run measures the selected workload and nothing else: set-up, the W warm-up steps, the K timed steps,
+the result line (`ms_per_step` = wall milliseconds of one timed step).  `--full` adds everything else the line
+used to carry (the extra objects below: other configs, rooflines, CPU baselines, the benchmark_pes.py suite).
+`--dump-outputs DIR` writes what the timed path returned in its last timed step to DIR/<workload>.npy
+(float32, frames x channels; rank 0): the inputs depend on the arguments only, so two builds can be compared
+output for output.
 
 Launching.  `--gpus N` with N > 1 and no WORLD_SIZE in the environment: this process only spawns N fresh
 rank processes (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_ADDR / MASTER_PORT set, one per GPU), relays rank 0's
@@ -22,9 +30,9 @@ mono, one step = one contiguous render(start, 1_000_000) through the public PE A
 NullRenderer graph, inputs generated on the device, outputs left in HBM.  With --gpus N every rank renders
 its own replica of the chain (a single biquad chain is one sequence: "replicas only").  The workloads that
 shard (c4, c5, supersaw: inputs of the root MixPE dealt i mod N over the ranks, one RCCL all-reduce of the
-partial mix per block) are selected with --workload and are reported inside the default line as well.
+partial mix per block) are selected with --workload and are reported inside a --full line as well.
 
-Extra objects in the default line (rank 0, N = 1): roofline / roofline_scaled (the C2 filter kernel, HIP
+Extra objects in a --full line (rank 0, N = 1): roofline / roofline_scaled (the C2 filter kernel, HIP
 events), cpu_baseline (the CPU oracle on this host, 1 thread, host core count stated), value_with_d2h
 (the same C2 steps with every root Snippet read on the host: pinned buffer, async copy overlapped with the
 next step -- and with a sync per step), cases (the other BASELINE configs, each with its CPU figure), suite
@@ -61,8 +69,12 @@ def parse_args(argv=None):
     ap.add_argument("--steps", type=int, default=20000)
     ap.add_argument("--warmup", type=int, default=2000)
     ap.add_argument("--workload", default="c2", choices=["c1", "c2", "c3", "c4", "c5", "supersaw"])
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU oracle timings")
-    ap.add_argument("--no-extras", action="store_true", help="primary workload only")
+    ap.add_argument("--full", action="store_true",
+                    help="also the side measurements: other configs, rooflines, CPU baselines, the benchmark_pes.py suite")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's output of the workload to DIR/<workload>.npy (float32)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU oracle timings")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: primary workload only")
     ap.add_argument("--dry-run", action="store_true",
                     help="launch glue only (CPU host): ranks rendezvous and report, nothing is rendered")
     ap.add_argument("--allow-no-rccl", action="store_true",
@@ -280,7 +292,7 @@ class Dist:
 
 
 class _Solo:
-    """The rank-local stand-in used for the N = 1 side measurements of a default run."""
+    """The rank-local stand-in used for the N = 1 side measurements of a --full run."""
     world, rank, enabled = 1, 0, False
 
     def barrier(self):
@@ -310,6 +322,23 @@ def timed_steps(dist, step, steps: int, warmup: int, finish=None):
     return dist.max_over_ranks(dt)
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(directory: str, last: dict) -> None:
+    """--dump-outputs: each workload's last timed step, its Snippets joined in order, as DIR/<name>.npy
+    (float32, frames x channels).  Read after the timed region."""
+    arrays = {name: np.concatenate([np.asarray(s.data, dtype=np.float32) for s in snippets])
+              for name, snippets in last.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT_BYTES, f"outputs of {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte dump limit"
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        path = os.path.join(directory, f"{name}.npy")
+        np.save(path, a)
+        print(f"[bench] wrote {path} {a.shape} {a.dtype}", file=sys.stderr, flush=True)
+
+
 def host_info():
     model = ""
     try:
@@ -337,7 +366,8 @@ def c2_graph(pg):
     return pe, r
 
 
-def bench_c2(pg, dist, steps, warmup, frames=1_000_000):
+def bench_c2(pg, dist, steps, warmup, frames=1_000_000, last=None):
+    """last: a dict that receives the last timed step's Snippets (list under "c2"), or None."""
     pe, r = c2_graph(pg)
     keep = {}
     # The timed steps start away from the warm-up stream: every frame of the timed region is rendered inside it (a
@@ -361,6 +391,8 @@ def bench_c2(pg, dist, steps, warmup, frames=1_000_000):
         _step(i)
 
     dt = timed_steps(dist, warm_done, steps, warmup)
+    if last is not None:
+        last["c2"] = [keep["s"]]
     r.stop()
     bench_c2.rendered = {"frames_rendered_in_timed_region": look_ahead.STATS["window_frames"] - before["window_frames"],
                          "frames_counted": frames * steps,
@@ -627,8 +659,9 @@ def cpu_c2(frames, budget_s=12.0):
 
 
 # ----------------------------------------------------------------------------- C1 and the small-block cases
-def bench_c1(pg, dist, steps, warmup):
-    """C1: GainPE(SinePE(440, ch=2), 0.5), 44.1 kHz, 431 blocks of 1024 (441 000 frames) per step."""
+def bench_c1(pg, dist, steps, warmup, last=None):
+    """C1: GainPE(SinePE(440, ch=2), 0.5), 44.1 kHz, 431 blocks of 1024 (441 000 frames) per step.
+    last: a dict that receives the last timed step's Snippets (list under "c1"), or None."""
     pg.set_sample_rate(44100)
     pe = pg.GainPE(pg.SinePE(frequency=440.0, amplitude=1.0, phase=0.0, channels=2), gain=0.5)
     r = pg.NullRenderer(sample_rate=44100)
@@ -636,15 +669,21 @@ def bench_c1(pg, dist, steps, warmup):
     r.start()
     total = 441_000
     keep = {}
+    final = warmup + steps - 1 if last is not None else -1
 
     def step(i):
+        blocks = keep["blocks"] = [] if i == final else None
         pos = 0
         while pos < total:
             n = min(1024, total - pos)
             keep["s"] = pe.render(pos, n)
+            if blocks is not None:
+                blocks.append(keep["s"])
             pos += n
 
     dt = timed_steps(dist, step, steps, warmup)
+    if last is not None:
+        last["c1"] = keep["blocks"]
     r.stop()
     return dt, total
 
@@ -767,10 +806,11 @@ def c3_inputs(frames):
     return x, h
 
 
-def bench_c3(pg, dist, steps, warmup, frames=96_000, block=None):
+def bench_c3(pg, dist, steps, warmup, frames=96_000, block=None, last=None):
     """C3: ConvolvePE(stereo ArrayPE, 65 536-tap FIR, fft_size=131072), 48 kHz; a step renders the whole
     `frames`-long signal, in one call or in `block`-frame calls, from stream position 0 (the overlap
-    history is carried from block to block and across steps)."""
+    history is carried from block to block and across steps).
+    last: a dict that receives the last timed step's Snippets (list under "c3"), or None."""
     pg.set_sample_rate(48000)
     x, h = c3_inputs(frames)
     pe = pg.ConvolvePE(pg.ArrayPE(x), pg.ArrayPE(h), fft_size=131072)
@@ -778,18 +818,24 @@ def bench_c3(pg, dist, steps, warmup, frames=96_000, block=None):
     r.set_source(pe)
     r.start()
     keep = {}
+    final = warmup + steps - 1 if last is not None else -1
 
     def step(i):
         if block is None:
             keep["s"] = pe.render(0, frames)
             return
+        blocks = keep["blocks"] = [] if i == final else None
         pos = 0
         while pos < frames:
             n = min(block, frames - pos)
             keep["s"] = pe.render(pos, n)
+            if blocks is not None:
+                blocks.append(keep["s"])
             pos += n
 
     dt = timed_steps(dist, step, steps, warmup)
+    if last is not None:
+        last["c3"] = [keep["s"]] if block is None else keep["blocks"]
     r.stop()
     return dt, frames
 
@@ -857,10 +903,10 @@ def cpu_c3(frames=96_000, budget_s=6.0):
 
 
 # ----------------------------------------------------------------------------- sharded mixes (C4, C5, SuperSaw)
-def mix_entry(pg, dist, config, steps, warmup, with_cpu):
+def mix_entry(pg, dist, config, steps, warmup, with_cpu, last=None):
     from pygmu2_amd.sharding import bench_voice_mix
     voices = 64 if config in ("c4", "c4r06") else 512
-    dt, frames, name, info = bench_voice_mix(pg, dist, steps, warmup, voices=voices, config=config)
+    dt, frames, name, info = bench_voice_mix(pg, dist, steps, warmup, voices=voices, config=config, last=last)
     per_voice = {"c4": 7, "c4r06": 7, "c5": 1, "supersaw": 7}[config]
     out = {"value": round(frames * steps / dt / 1e6, 3), "unit": "Msamples/s",
            "ms_per_block": round(dt / steps * 1e3, 4), "scaling": "strong", "workload": name,
@@ -1161,9 +1207,11 @@ def main():
         sys.exit(1)
 
     n_gpus = max(1, dist.world)
-    with_cpu = not args.no_cpu and n_gpus == 1
-    result = {}
+    with_cpu = args.full and not args.no_cpu and n_gpus == 1
+    extras = args.full and not args.no_extras
+    warm = {}
     extra_primary = {}
+    last = {} if args.dump_outputs and dist.rank == 0 else None
     if args.workload == "c2":
         # A process that has just started is not the process that renders: the first windows it opens run through cold
         # Python / ctypes paths, and the chip reaches the clock it holds over a stream only after ~20 ms of work.  The
@@ -1174,29 +1222,33 @@ def main():
         process_warmup = int(os.environ.get("PGX_BENCH_PROCESS_WARMUP", "10"))
         for _ in range(process_warmup):
             bench_c2(pg, dist, 2000, 20)
-        result["process_warmup"] = (f"{process_warmup} untimed C2 streams of 2 000 steps on other PE objects before the "
-                                    f"{args.warmup} warm-up steps" if process_warmup else "none")
-        result["process_warmup_streams"] = process_warmup
-        dt, frames = bench_c2(pg, dist, args.steps, args.warmup)
+        warm["process_warmup"] = (f"{process_warmup} untimed C2 streams of 2 000 steps on other PE objects before the "
+                                  f"{args.warmup} warm-up steps" if process_warmup else "none")
+        warm["process_warmup_streams"] = process_warmup
+        dt, frames = bench_c2(pg, dist, args.steps, args.warmup, last=last)
         name = "C2: BiquadPE(SinePE(440), lowpass 1 kHz, q 0.707), 44.1 kHz mono, render(start, 1_000_000) per step"
         units = frames * args.steps * n_gpus
     elif args.workload == "c1":
-        dt, frames = bench_c1(pg, dist, args.steps, args.warmup)
+        dt, frames = bench_c1(pg, dist, args.steps, args.warmup, last=last)
         name = "C1: GainPE(SinePE(440, ch=2), 0.5), 44.1 kHz stereo, 431 blocks of 1024 per step"
         units = frames * args.steps * n_gpus
     elif args.workload == "c3":
-        dt, frames = bench_c3(pg, dist, args.steps, args.warmup)
+        dt, frames = bench_c3(pg, dist, args.steps, args.warmup, last=last)
         name = "C3: ConvolvePE stereo x 65536-tap FIR, 48 kHz, 96 000 frames per step"
         units = frames * args.steps * n_gpus
     else:
-        entry = mix_entry(pg, dist, args.workload, args.steps, args.warmup, with_cpu and dist.rank == 0)
+        entry = mix_entry(pg, dist, args.workload, args.steps, args.warmup, with_cpu and dist.rank == 0, last=last)
         dt, frames, name = entry.pop("_dt"), 48_000, entry["workload"]
         units = frames * args.steps
         extra_primary = {k: entry[k] for k in entry if k not in ("value", "unit", "workload", "steps", "warmup")}
 
+    if last is not None:
+        dump_outputs(args.dump_outputs, last)
+        last = None
+
     value = units / dt / 1e6
     sharded = args.workload in SHARDED
-    result.update({
+    result = {
         "metric": "Msamples/s rendered (benchmark_pes.py metric: output frames / wall second)",
         "value": round(value, 3), "unit": "Msamples/s", "n_gpus": n_gpus, "n_ranks_seen": ranks_seen,
         "steps": args.steps,
@@ -1208,7 +1260,8 @@ def main():
                    "parallelism": (f"inputs of the root MixPE dealt i mod {n_gpus} over the ranks, one RCCL all-reduce "
                                    "of the partial mix per block (pgx_allreduce_sum)" if sharded else
                                    ("single chain" if n_gpus == 1 else f"{n_gpus} independent replicas (replicas only)"))},
-    })
+    }
+    result.update(warm)
     if sharded:
         result["mix"] = extra_primary
         if "roofline" in extra_primary:
@@ -1220,11 +1273,11 @@ def main():
         result["collective"] = dist.collective
         if dist.collective != "rccl":
             result["n_ranks_present"] = getattr(dist, "ranks_present", 0)      # counted through the store, not by RCCL
-    if not sharded and not args.no_extras and dist.enabled and dist.collective != "rccl":
+    if not sharded and extras and dist.enabled and dist.collective != "rccl":
         note = {"error": f"no RCCL communicator ({dist.collective_error}): the sharded mixes were not run"}
         result["voice_mix"], result["supersaw_mix"] = dict(note), dict(note)
-    elif not sharded and not args.no_extras:
-        # collectives: every rank takes part.  The sharded mixes ride along in the default line.
+    elif not sharded and extras:
+        # collectives: every rank takes part.  The sharded mixes ride along in a --full line.
         # (streams of a few hundred blocks -- 40 - 60 ms of device time: over 50 blocks the chip has not yet reached the clock
         # a stream runs at, and the same kernels took 5 - 7 % longer: DESIGN 7)
         # (C5 renders in windows of 2, 4, 8 blocks since its voices are mixed on chip: 384 after 47, as for the SuperSaw mix below)
@@ -1239,7 +1292,7 @@ def main():
             result["ladder_mix"] = mix_entry(pg, dist, "c4", 256, 63, False)
             result["ladder_mix"].pop("_dt")
 
-    if dist.rank == 0 and not args.no_extras and not sharded:
+    if dist.rank == 0 and extras and not sharded:
         solo = _Solo()
         result["device"] = device.device_name()
         # the filter kernel as the C2 steps launch it: look-ahead renders `ahead` 1 M-frame steps per launch

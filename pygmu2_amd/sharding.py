@@ -407,11 +407,12 @@ def mix_voice_factory(config: str):
             "c4r06": (c4_res06_voice, 64)}[config]
 
 
-def bench_voice_mix(pg, dist, steps, warmup, voices=512, block=48_000, config="c5"):
+def bench_voice_mix(pg, dist, steps, warmup, voices=512, block=48_000, config="c5", last=None):
     """Sharded MixPE of BASELINE config 5 (512 voices), config 4 (64 SuperSaw->Ladder instances) or the
     512-voice SuperSaw mix: inputs i = rank (mod world) on each GPU, one RCCL all-reduce of the (block, 1)
     partial mix per rendered block.  Strong scaling.  `dist` offers world / rank / enabled / barrier() /
-    max_over_ranks(); the communicator (pygmu2_amd.comm) is already up when world > 1."""
+    max_over_ranks(); the communicator (pygmu2_amd.comm) is already up when world > 1.  `last`: a dict that
+    receives the last timed block's Snippet (a one-element list under `config`), or None."""
     import time
 
     from . import device
@@ -461,6 +462,8 @@ def bench_voice_mix(pg, dist, steps, warmup, voices=512, block=48_000, config="c
     device.synchronize()               # ... and wait for it: every block is rendered AND reduced
     dist.barrier()
     dt = dist.max_over_ranks(time.perf_counter() - t0)
+    if last is not None:
+        last[config] = [keep["s"]]
     calls1 = (getattr(root._reducer, "calls", 0), getattr(root._reducer, "floats", 0))
     # what a block costs this rank before the exchange: the same stream continued on the rank-local mix alone (no
     # collective), and with it what the blocks above spent waiting for the slowest rank and the links

@@ -57,7 +57,7 @@ def test_two_ranks_without_a_communicator_fail_unless_told_otherwise():
     n_ranks_seen = 0 / collective "store" and say that the sharded mixes were not run.  On a box with two GPUs the
     communicator exists and both runs are ordinary.  Either way stdout is exactly one JSON line (RCCL's greeting
     banner goes to stderr)."""
-    args = ["--gpus", "2", "--steps", "5", "--warmup", "1", "--no-cpu"]
+    args = ["--gpus", "2", "--steps", "5", "--warmup", "1", "--full", "--no-cpu"]
     p = _run(args, env={"PGX_BENCH_RCCL_TIMEOUT": "60"}, timeout=400)
     lines = [l for l in p.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, lines
@@ -116,3 +116,59 @@ def test_flat_keys_are_scalars_and_cover_the_north_star_numbers():
                 "c3_96000_traffic_over_algorithmic", "ladder_res06_pipelined", "ladder_res06_cpu", "c4_res06_msamples_s",
                 "c2_roofline_fp64_frac", "supersaw_roofline_fp64_frac", "c5_cpu_msamples_s"):
         assert key in flat, key
+
+
+def test_dump_outputs_joins_the_last_step_in_order(tmp_path):
+    """--dump-outputs: the Snippets of the last timed step, joined in order, one float32 .npy per workload."""
+    sys.path.insert(0, ROOT)
+    import numpy as np
+
+    import bench
+    import pygmu2_amd as pg
+    rng = np.random.default_rng(7)
+    a, b = rng.standard_normal((1024, 2)).astype(np.float32), rng.standard_normal((300, 2)).astype(np.float32)
+    bench.dump_outputs(str(tmp_path / "out"), {"c1": [pg.Snippet(0, a), pg.Snippet(1024, b)]})
+    got = np.load(tmp_path / "out" / "c1.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, np.concatenate([a, b]))
+    assert sorted(os.listdir(tmp_path / "out")) == ["c1.npy"]
+
+
+def test_plain_run_options():
+    sys.path.insert(0, ROOT)
+    import bench
+    args = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert args.steps == 7 and args.warmup == 2 and not args.full and args.dump_outputs is None
+    args = bench.parse_args(["--full", "--dump-outputs", "d"])
+    assert args.full and args.dump_outputs == "d"
+
+
+@pytest.mark.gpu
+def test_plain_run_is_the_headline_and_dumps_its_last_step(tmp_path):
+    """A plain run prints the C2 line alone (no side measurements), times exactly --steps steps, and
+    --dump-outputs writes the last timed step's 1 M frames, which match the CPU oracle."""
+    from oracle import pe_oracle as O
+    import numpy as np
+    steps, warmup, frames = 3, 2, 1_000_000
+    p = _run(["--gpus", "1", "--steps", str(steps), "--warmup", str(warmup), "--dump-outputs", str(tmp_path)],
+             timeout=600)
+    assert p.returncode == 0, p.stdout[-1000:] + p.stderr[-3000:]
+    lines = [l for l in p.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, lines
+    d = json.loads(lines[0])
+    assert next(iter(d)) == "metric"
+    assert d["unit"] == "Msamples/s" and d["higher_is_better"] is True and d["dtype"] == "f64" and d["value"] > 0
+    assert d["steps"] == steps and d["warmup"] == warmup and d["ms_per_step"] > 0
+    assert d["config"]["frames_counted"] == steps * frames
+    for side in ("roofline", "cpu_baseline", "voice_mix", "supersaw_mix", "cases", "suite", "north_star_pes",
+                 "value_with_d2h"):
+        assert side not in d, side
+    got = np.load(tmp_path / "c2.npy")
+    assert got.shape == (frames, 1) and got.dtype == np.float32
+    # the timed steps are one stream from (warmup + 1000) x frames on; the filter forgets its start within a few
+    # hundred frames, so the oracle starts 4096 frames early from rest
+    pos, pre = (warmup + 1000 + steps - 1) * frames, 4096
+    x = O.sine_pure(pos - pre, pre + frames, 440.0, sr=44100)
+    want = O.biquad_const(O.biquad_state(1), x, 1000.0, 0.707, "lowpass", 0.0, 44100)[pre:]
+    peak = float(np.max(np.abs(want)))
+    err = float(np.max(np.abs(got.astype(np.float64) - want)))
+    assert err <= 1e-5 * peak, (err, peak)

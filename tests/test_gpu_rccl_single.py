@@ -306,7 +306,7 @@ def test_bench_distributed_glue_single_rank(tmp_path):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"),
-           "--gpus", "1", "--steps", "3", "--warmup", "1", "--no-cpu"]
+           "--gpus", "1", "--steps", "3", "--warmup", "1", "--full", "--no-cpu"]
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-3000:]
     import json
