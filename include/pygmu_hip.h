@@ -686,6 +686,47 @@ int pgx_allreduce_sum(float *out, const float *in, size_t n, int64_t *ticket);
 int pgx_allreduce_wait(int64_t ticket);
 int pgx_allreduce_scalar_host(double *value_host, int op);
 
+/* ------------------------------------------------------------------ KarplusStrongPE / AnalogOscPE (pgx_sources.hip)
+ * KarplusStrongPE._render (karplus_strong_pe.py:137-213): a one-period circular line of float32 noise (drawn and
+ * uploaded by the caller at the first render after a reset; state zeroed), fed back through the two-point average
+ * times rho and a first-order allpass, in the reference's float32 operation order: bit-exact.  `batch` strings, each
+ * with its own params[i], line (lines + params[i].line_offset, params[i].n floats) and state[i]; string i writes n
+ * frames of `channels` identical copies at out + i * out_stride.  start = absolute index of the first generated frame
+ * (>= 0: the caller zero-fills frames before 0), which the two-phase switch is compared with.  max_line >= every
+ * params[i].n: lines of a workgroup's strings that fit in 64 KiB are staged in LDS for the render. */
+typedef struct {
+    int64_t line_offset;   /* floats from `lines` to this string's line */
+    int32_t n;             /* N = max(2, floor(sr / f)) */
+    int32_t two_phase;     /* duration and rho_damping both given */
+    int64_t switch_at;     /* absolute frame from which rho_damping applies */
+    float rho;             /* float32(rho), float32(rho_damping), float32(allpass c) */
+    float rho_damping;
+    float c;
+    float pad;
+} pgx_ks_params;
+typedef struct {
+    int32_t r;             /* read position */
+    float ap_in;           /* allpass input / output of the previous frame */
+    float ap_out;
+    int32_t pad;
+} pgx_ks_state;
+int pgx_karplus_strong(float *out, int64_t out_stride, int batch, int64_t start, int64_t n, int channels,
+                       const pgx_ks_params *params, float *lines, pgx_ks_state *state, int max_line);
+
+/* AnalogOscPE._render (analog_osc_pe.py:203-267), float64 inside, float32 out, `channels` identical copies.
+ * waveform 0 = "rectangle", 1 = "sawtooth".  Pure form (scalar parameters): phase = mod(index * f / sr, 1)
+ * (:185-187); the sawtooth integrates its corrected derivative from y0 = _piecewise_linear_value(phase[0]) within
+ * this render (:253-256).  Stateful form: freq_stream / duty_stream are optional float32 (frames, 1) streams
+ * overriding the scalar; state = { carried phase, carried saw value } (:189-193, :262-263); restart != 0 (a render not
+ * contiguous with the previous one) starts from phase 0 / saw -1.  workspace: pgx_analog_osc_workspace_bytes(n)
+ * bytes of device scratch (the pure rectangle needs none). */
+size_t pgx_analog_osc_workspace_bytes(int64_t n);
+int pgx_analog_osc_pure(float *out, int64_t start, int64_t n, int channels, double sample_rate, int waveform,
+                        double freq, double duty, void *workspace);
+int pgx_analog_osc_stateful(float *out, int64_t n, int channels, double sample_rate, int waveform, double freq,
+                            double duty, const float *freq_stream, const float *duty_stream, int restart,
+                            double *state /* [2] */, void *workspace);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,7 +6,8 @@ ProcessingElement / SourcePE / Snippet / Extent / Renderer / NullRenderer and th
 SinePE, BlitSawPE, SuperSawPE, BiquadPE, LadderPE, CombPE, MixPE, GainPE, ConvolvePE,
 AdsrGatedPE, AdsrTriggeredPE, PeriodicGate, PeriodicTrigger, ConstantPE, ArrayPE,
 DiracPE, IdentityPE, CachePE, CropPE, SVFilterPE, EnvelopePE, TransformPE, DelayPE, PiecewisePE,
-TriggerRestartPE, ReverbPE, WavWriterPE, WavReaderPE (+ render_to_file).  Snippet payloads live in HBM; all DSP runs in
+TriggerRestartPE, ReverbPE, WavWriterPE, WavReaderPE, KarplusStrongPE, AnalogOscPE (+ render_to_file,
+rho_for_decay_db).  Snippet payloads live in HBM; all DSP runs in
 hand-written HIP kernels for gfx950 behind the C ABI of include/pygmu_hip.h.
 """
 
@@ -54,6 +55,8 @@ from .dynamics_pe import DynamicsMode, DynamicsPE, db_to_ratio, ratio_to_db
 from .compressor_pe import CompressorPE, ExpanderPE, LimiterPE
 from .wav_writer_pe import WavWriterPE
 from .wav_reader_pe import WavReaderPE
+from .karplus_strong_pe import KarplusStrongPE, rho_for_decay_db
+from .analog_osc_pe import AnalogOscPE
 from .utils import render_to_file
 from . import device, diagnostics
 
@@ -68,4 +71,5 @@ __all__ = [
     "ReverbPE", "SpatialPE", "SpatialMethod", "SpatialAdapter", "SpatialLinear", "SpatialConstantPower",
     "SpatialHRTF", "LoopPE", "WindowMode", "WindowPE", "DynamicsMode", "DynamicsPE", "CompressorPE", "LimiterPE",
     "ExpanderPE", "db_to_ratio", "ratio_to_db", "WavWriterPE", "WavReaderPE", "render_to_file", "device", "diagnostics",
+    "KarplusStrongPE", "rho_for_decay_db", "AnalogOscPE",
 ]

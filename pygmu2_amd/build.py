@@ -31,6 +31,7 @@ SOURCES = [
     "pgx_dynamics.hip",
     "pgx_fftconv.hip",
     "pgx_comm.hip",
+    "pgx_sources.hip",
 ]
 
 # -ffp-contract=off: the parity contract is "same float64 operation order as the reference's

@@ -163,6 +163,10 @@ _SIGNATURES = [
     ("pgx_allreduce_sum", _I, [_P, _P, _Z, C.POINTER(_L)]),
     ("pgx_allreduce_wait", _I, [_L]),
     ("pgx_allreduce_scalar_host", _I, [C.POINTER(_D), _I]),
+    ("pgx_karplus_strong", _I, [_P, _L, _I, _L, _L, _I, _P, _P, _P, _I]),
+    ("pgx_analog_osc_workspace_bytes", _Z, [_L]),
+    ("pgx_analog_osc_pure", _I, [_P, _L, _L, _I, _D, _I, _D, _D, _P]),
+    ("pgx_analog_osc_stateful", _I, [_P, _L, _I, _D, _I, _D, _D, _P, _P, _I, _P, _P]),
 ]
 
 EXPORTED_SYMBOLS = [s[0] for s in _SIGNATURES]
@@ -183,6 +187,9 @@ LADDER_PARAMS = np.dtype([("freq", "<f8"), ("resonance", "<f8"), ("drive", "<f8"
 COMB_PARAMS = np.dtype([("feedback", "<f8"), ("delay", "<i4"), ("buffer_len", "<i4")])
 TRANSFORM_OP = np.dtype([("code", "<i4"), ("pad", "<i4"), ("p0", "<f8"), ("p1", "<f8")])
 GATE_PARAMS = np.dtype([("dt", "<f8"), ("phase", "<f8"), ("duty", "<f8")])
+KS_PARAMS = np.dtype([("line_offset", "<i8"), ("n", "<i4"), ("two_phase", "<i4"), ("switch_at", "<i8"),
+                      ("rho", "<f4"), ("rho_damping", "<f4"), ("c", "<f4"), ("pad", "<f4")])
+KS_STATE = np.dtype([("r", "<i4"), ("ap_in", "<f4"), ("ap_out", "<f4"), ("pad", "<i4")])
 ADSR_PARAMS = np.dtype([("attack_dvdt", "<f8"), ("decay_dvdt", "<f8"), ("release_dvdt", "<f8"),
                         ("sustain_level", "<f8"), ("sustain_samples", "<i8")])
 
