@@ -215,6 +215,11 @@ int pgx_biquad_sine(float *out, int64_t start, int64_t n, double sample_rate, do
                     const double *coef /* [5] */, const double *tables, int64_t settle_frames,
                     double *state /* [2] */,
                     double *state_backup /* [2] or NULL: receives the state on entry (a window's snapshot) */);
+/* Blocks long enough that every wave of one resident round gets a run of at least min_chunks 1024-frame chunks are
+ * rendered by the wave-run kernel (k_biquad_sine_runs), shorter ones by the single-launch filter kernel.  0 turns
+ * the wave runs off (environment: PGX_SB_SINE_RUNS), a negative value restores the default.  Returns the previous
+ * value.  pgx_biquad_sine_supported answers the same either way. */
+int pgx_biquad_sine_set_runs(int min_chunks);
 
 /* Time-varying coefficients: _compute_coefficients per sample (biquad_pe.py:217-335) +
  * the direct-form-I recurrence of _biquad_varying_numba (biquad_pe.py:35-62).

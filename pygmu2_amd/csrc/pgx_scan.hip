@@ -941,6 +941,191 @@ k_biquad_settled(float *__restrict__ out, int64_t out_stride, const float *__res
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// Wave runs: BiquadPE(SinePE) over window-sized blocks (pgx_biquad_sine when every wave gets a long run).
+// The filter forgets (settle_frames), so a wave needs no carry-in from any other wave: each wave owns a contiguous
+// run of 1024-frame chunks (64 lanes x 16 frames), warms up from zero state over the `warm` chunks in front of it
+// (outputs discarded) and carries its own state from chunk to chunk, A^1024 carry + e(lane 63): a readlane and four
+// fused multiply-adds.  No barrier and no LDS exchange between waves, so the waves of a CU overlap freely; the grid
+// is one resident round (the occupancy the runtime reports), so there is no tail round either.
+// Per chunk the arithmetic is k_biquad_settled<.., SINE>'s: the same sine, zero-state pass, DPP row scan and pass 2.
+// Wave 0 renders the chunks [0, head) and the tail [tail_start, chunks): it alone reads the carried state (first
+// thing) and writes it (last thing).  Wave g >= 1 renders `run` chunks from head + (g-1)*run.  head >= warm.
+// ------------------------------------------------------------------------------------------------
+struct SbRuns {
+    double w, amp, phase0, sr, inv_sr, cos_d, sin_d;
+    double two_cos_d;            // 2 cos(w / sr) for the three-term recurrence, or 0: rotate (very low frequencies)
+    double chunk_cos, chunk_sin; // cos / sin of a chunk's advance, 1024 frames of w / sr (the angle reduced on the host)
+    int64_t start;
+    double *state_backup;        // receives the carried state on entry (a look-ahead window's snapshot), or nullptr
+};
+constexpr int kRunChunk = 64 * kBqT;     // 1024 frames: a wave's step
+constexpr int kRunBlock = 256;           // four independent waves per workgroup (they share only rows_lds)
+#ifndef PGX_SB_RUNS_WAVES
+#define PGX_SB_RUNS_WAVES 4              // waves per SIMD k_biquad_sine_runs is compiled for
+#endif
+
+// the 16 frames of a lane from the (sin, cos) of its first one, as k_biquad_settled<.., SINE>'s request() makes them
+__device__ __forceinline__ void runs_sine16(const SbRuns &sine, double sn, double cs, float (&x)[kBqT]) {
+    if (PGX_HOT(sine.two_cos_d != 0.0)) {
+        double s0 = sn, s1 = __builtin_fma(cs, sine.sin_d, sn * sine.cos_d);
+        if (PGX_HOT(sine.amp == 1.0)) {
+            x[0] = (float)s0;
+            x[1] = (float)s1;
+#pragma unroll
+            for (int j = 2; j < kBqT; ++j) {
+                const double s2 = __builtin_fma(sine.two_cos_d, s1, -s0);
+                x[j] = (float)s2;
+                s0 = s1;
+                s1 = s2;
+            }
+            return;
+        }
+        x[0] = (float)(sine.amp * s0);
+        x[1] = (float)(sine.amp * s1);
+#pragma unroll
+        for (int j = 2; j < kBqT; ++j) {
+            const double s2 = __builtin_fma(sine.two_cos_d, s1, -s0);
+            x[j] = (float)(sine.amp * s2);
+            s0 = s1;
+            s1 = s2;
+        }
+        return;
+    }
+#pragma unroll
+    for (int j = 0; j < kBqT; ++j) {
+        x[j] = (float)(sine.amp * sn);
+        const double s2 = __builtin_fma(cs, sine.sin_d, sn * sine.cos_d);
+        cs = __builtin_fma(-sn, sine.sin_d, cs * sine.cos_d);
+        sn = s2;
+    }
+}
+
+__device__ __forceinline__ double readlane63_f64(double v) {
+    const int lo = __builtin_amdgcn_readlane(__double2loint(v), 63);
+    const int hi = __builtin_amdgcn_readlane(__double2hiint(v), 63);
+    return __hiloint2double(hi, lo);
+}
+
+__global__ void __launch_bounds__(kRunBlock, PGX_SB_RUNS_WAVES)
+k_biquad_sine_runs(float *__restrict__ out, int64_t n, const double *__restrict__ coef,
+                   const double *__restrict__ tables, double *state, int run, int head, int tail, int warm, int waves,
+                   SbRuns sine) {
+    __shared__ __attribute__((aligned(16))) float stage_lds[(kRunBlock / 64) * kStageWords];
+    __shared__ __attribute__((aligned(16))) double rows_lds[2 * kBqT];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const double *tb = tables;
+    // the first rows of A^j (pass 2), read as LDS broadcasts (see k_biquad_settled): the kernel's only barrier
+    if (tid < 2 * kBqT) rows_lds[tid] = tb[kBqRowsAt + tid];
+    __syncthreads();
+    const int g = blockIdx.x * (kRunBlock / 64) + wave;
+    if (g >= waves) return;
+
+    float *wlds = stage_lds + wave * kStageWords;
+    const bool io_aligned = aligned16(out);
+    const int64_t chunks = (n + kRunChunk - 1) / kRunChunk;
+    int64_t tail_start = chunks - tail;
+    if (tail_start < head) tail_start = head;
+
+    const double b0 = coef[0], b1 = coef[1], b2 = coef[2], a1 = coef[3], a2 = coef[4];
+    M2 pstep[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) pstep[k] = load_m2(tb + 4 * k);
+    const M2 pwave = load_m2(tb + 24);
+    const M2 mlane = load_m2(tb + 28 + 4 * lane);
+    const M2 m16 = load_m2(tb + 28 + 4 * ((lane & 15) + 1));
+    const M2 m32 = load_m2(tb + 28 + 4 * ((lane & 31) + 1));
+
+    // renders the chunks [cb, ce) after `warm` chunks of warm-up (from the carried state at chunk 0).  Called once per
+    // range, not from a loop over the ranges: the sine's constants are then not hoisted into registers for all of it
+    auto render = [&](const int64_t cb, const int64_t ce) {
+        int64_t c = cb == 0 ? 0 : cb - warm;
+        V2 carry{0.0, 0.0};
+        if (cb == 0) {
+            carry = V2{state[0], state[1]};
+            if (sine.state_backup && lane == 0) {              // wave 0 alone reads and writes the state
+                sine.state_backup[0] = carry.x;
+                sine.state_backup[1] = carry.y;
+            }
+        }
+        // the lane's first frame: k_sine's evaluation for the first chunk, then turned by a chunk's advance
+        double sn, cs;
+        {
+            const double t = pgx::pgx_div_by((double)(sine.start + c * kRunChunk + lane * kBqT), sine.sr, sine.inv_sr);
+            pgx::pgx_sincos_bounded(sine.phase0 + sine.w * t, sn, cs);
+        }
+#pragma nounroll
+        for (; c < ce; ++c) {
+            float xf[kBqT];
+            runs_sine16(sine, sn, cs, xf);
+            // zero-state response of the lane's 16 frames
+            V2 e{0.0, 0.0};
+            const double na1 = -a1, na2 = -a2;
+            double yz[kBqT];
+#pragma unroll
+            for (int j = 0; j < kBqT; ++j) {
+                const double x = (double)xf[j];
+                const double y = __builtin_fma(b0, x, e.x);
+                e.x = __builtin_fma(na1, y, __builtin_fma(b1, x, e.y));
+                e.y = __builtin_fma(na2, y, b2 * x);
+                yz[j] = y;
+            }
+            // inclusive scan over the wave (k_biquad_settled's)
+            e = mv_add_fma(pstep[0], dpp_v2<0x111, 0xf>(e), e);
+            e = mv_add_fma(pstep[1], dpp_v2<0x112, 0xf>(e), e);
+            e = mv_add_fma(pstep[2], dpp_v2<0x114, 0xf>(e), e);
+            e = mv_add_fma(pstep[3], dpp_v2<0x118, 0xf>(e), e);
+            e = mv_add_fma(m16, dpp_v2<0x142, 0xa>(e), e);
+            e = mv_add_fma(m32, dpp_v2<0x143, 0xc>(e), e);
+
+            const int64_t w0 = c * kRunChunk;
+            if (PGX_HOT(c >= cb)) {
+                const int64_t f0 = w0 + lane * kBqT;
+                const V2 ex = dpp_v2<0x138, 0xf>(e);           // previous lane's inclusive value, 0 for lane 0
+                const V2 zin = mv_add_fma(mlane, carry, ex);
+                float yf[kBqT];
+                const double *rows = rows_lds;
+#pragma unroll
+                for (int j = 0; j < kBqT; ++j)
+                    yf[j] = (float)__builtin_fma(rows[2 * j], zin.x, __builtin_fma(rows[2 * j + 1], zin.y, yz[j]));
+                if (PGX_HOT(io_aligned && w0 + kRunChunk <= n))
+                    stage_store(wlds, out + w0, lane, yf);
+                else
+                    store_frames<kBqT>(out, f0, n, 1, 0, yf);
+                if (PGX_COLD(f0 <= n - 1 && n - 1 - f0 < kBqT)) {  // the lane holding the last frame: new state
+                    // its frames made again (bit for bit the same), rather than kept in 16 registers for this branch
+                    double rs = sn, rc = cs;
+                    asm volatile("" : "+v"(rs), "+v"(rc));
+                    runs_sine16(sine, rs, rc, xf);
+                    V2 z = zin;
+                    for (int j = 0; j <= (int)(n - 1 - f0); ++j) {
+                        double x = (double)xf[j];
+                        double y = z.x + b0 * x;
+                        double z0 = (z.y + b1 * x) - a1 * y;
+                        z.y = b2 * x - a2 * y;
+                        z.x = z0;
+                    }
+                    state[0] = z.x;
+                    state[1] = z.y;
+                }
+            }
+            // the wave's state after this chunk: what the state in front of it leaves, plus lane 63's inclusive value
+            carry = mv_add_fma(pwave, carry, V2{readlane63_f64(e.x), readlane63_f64(e.y)});
+            const double s2 = __builtin_fma(sn, sine.chunk_cos, cs * sine.chunk_sin);
+            cs = __builtin_fma(cs, sine.chunk_cos, -(sn * sine.chunk_sin));
+            sn = s2;
+        }
+    };
+    // the chunks of this wave, and for wave 0 the tail
+    if (g == 0) {
+        render(0, head < chunks ? head : chunks);
+        render(tail_start, chunks);
+    } else {
+        const int64_t cb = head + (int64_t)(g - 1) * run;
+        render(cb, cb + run < tail_start ? cb + run : tail_start);
+    }
+}
+
 struct BqPlan {
     int seg_tiles;
     int nseg;
@@ -4083,6 +4268,57 @@ int pgx_biquad_sine_supported(int64_t n, int64_t settle_frames) {
     return (n > 0 && biquad_sine_plan(n, settle_frames).ok) ? 1 : 0;
 }
 
+// Wave runs (k_biquad_sine_runs) for window-sized blocks.  The grid is one resident round: the occupancy the runtime
+// reports for the kernel times the CUs, taken once.
+constexpr int64_t kRunMinChunks = 4;     // a wave's run below this: the current kernel (measured faster from 16 M frames on)
+static int runs_resident_waves() {
+    static const int waves = [] {
+        int blocks = 0, cus = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, k_biquad_sine_runs, kRunBlock, 0) != hipSuccess ||
+            hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, pgx::device_index()) != hipSuccess)
+            return 0;
+        return blocks * cus * (kRunBlock / 64);
+    }();
+    return waves;
+}
+// The shortest run (in chunks) the wave runs take: PGX_SB_SINE_RUNS=0 forces the current kernel (A/B runs), another
+// value replaces kRunMinChunks; pgx_biquad_sine_set_runs overrides it
+static int &runs_min_chunks() {
+    static int v = getenv("PGX_SB_SINE_RUNS") ? atoi(getenv("PGX_SB_SINE_RUNS")) : (int)kRunMinChunks;
+    return v;
+}
+
+struct RunsPlan {
+    bool ok;
+    int run, head, tail, warm, waves;    // in 1024-frame chunks; waves used
+};
+static RunsPlan biquad_sine_runs_plan(int64_t n, int64_t settle_frames) {
+    RunsPlan p{};
+    const int resident = runs_resident_waves();
+    const int min_chunks = runs_min_chunks();
+    if (min_chunks <= 0 || resident <= 0 || settle_frames <= 0) return p;
+    const int64_t chunks = pgx::ceil_div(n, (int64_t)kRunChunk);
+    const int64_t warm = pgx::ceil_div(settle_frames, (int64_t)kRunChunk);
+    const int64_t run = pgx::ceil_div(chunks, (int64_t)resident);
+    if (run < min_chunks || run < 4 * warm) return p;       // short runs, or a warm-up above 1/4 of the work
+    const int64_t head = run / 2 > warm ? run / 2 : warm;    // wave 0: head + tail = one run
+    const int64_t tail = run - head > 1 ? run - head : 1;
+    if (chunks <= head + tail) return p;
+    p.ok = true;
+    p.run = (int)run;
+    p.head = (int)head;
+    p.tail = (int)tail;
+    p.warm = (int)warm;
+    p.waves = 1 + (int)pgx::ceil_div(chunks - head - tail, run);
+    return p;
+}
+
+int pgx_biquad_sine_set_runs(int min_chunks) {
+    const int was = runs_min_chunks();
+    runs_min_chunks() = min_chunks < 0 ? (int)kRunMinChunks : min_chunks;
+    return was;
+}
+
 int pgx_biquad_sine(float *out, int64_t start, int64_t n, double sample_rate, double w, double amp, double phase0,
                     const double *coef, const double *tables, int64_t settle_frames, double *state,
                     double *state_backup) {
@@ -4116,6 +4352,38 @@ int pgx_biquad_sine(float *out, int64_t start, int64_t n, double sample_rate, do
         c.tile_sin = (double)sinl(a);
         cached = c;
         have = true;
+    }
+    const RunsPlan rp = biquad_sine_runs_plan(n, settle_frames);
+    if (rp.ok) {
+        static SbRuns runs_cached;
+        static bool runs_have = false;
+        if (!runs_have || runs_cached.w != w || runs_cached.sr != sample_rate) {
+            SbRuns c;
+            c.w = cached.w;
+            c.sr = cached.sr;
+            c.inv_sr = cached.inv_sr;
+            c.cos_d = cached.cos_d;
+            c.sin_d = cached.sin_d;
+            c.two_cos_d = cached.two_cos_d;
+            // a chunk's advance, 1024 frames: the angle reduced in long double before the sine and cosine are taken
+            const long double turn = 6.283185307179586476925286766559L;
+            long double a = (long double)w / (long double)sample_rate * (long double)kRunChunk;
+            a -= turn * floorl(a / turn);
+            c.chunk_cos = (double)cosl(a);
+            c.chunk_sin = (double)sinl(a);
+            runs_cached = c;
+            runs_have = true;
+        }
+        SbRuns sine = runs_cached;
+        sine.amp = amp;
+        sine.phase0 = phase0;
+        sine.start = start;
+        sine.state_backup = state_backup;
+        const int groups = (rp.waves + kRunBlock / 64 - 1) / (kRunBlock / 64);
+        hipLaunchKernelGGL(k_biquad_sine_runs, dim3(groups), dim3(kRunBlock), 0, pgx::stream(), out, n, coef, tables,
+                           state, rp.run, rp.head, rp.tail, rp.warm, rp.waves, sine);
+        PGX_LAUNCH_CHECK("k_biquad_sine_runs");
+        return PGX_OK;
     }
     SbSine sine = cached;
     sine.amp = amp;
