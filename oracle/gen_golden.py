@@ -63,24 +63,35 @@ def load_reference():
                  "periodic_gate", "periodic_trigger", "convolve_pe", "svfilter_pe", "envelope_pe",
                  "transform_pe", "wavetable_pe", "delay_pe", "piecewise_pe", "trigger_restart_pe", "cache_pe",
                  "reverb_pe", "assets", "spatial_pe", "loop_pe", "window_pe", "conversions", "dynamics_pe",
-                 "compressor_pe"):
+                 "compressor_pe", "karplus_strong_pe", "analog_osc_pe"):
         mods[name] = importlib.import_module(f"pygmu2.{name}")
     return mods
 
 
-def build(spec, M):
-    """SPEC -> reference PE instance."""
+def build(spec, M, shared=None):
+    """SPEC -> reference PE instance (a node with `"share": <name>` is one instance wherever the name appears)."""
+    shared = {} if shared is None else shared
+    name = spec.get("share")
+    if name is not None and name in shared:
+        return shared[name]
+    pe = _build(spec, M, shared)
+    if name is not None:
+        shared[name] = pe
+    return pe
+
+
+def _build(spec, M, shared):
     kind = spec["pe"]
     kw = {}
     for k, v in spec.items():
-        if k == "pe":
+        if k in ("pe", "share"):
             continue
         if isinstance(v, dict) and "pe" in v:
-            kw[k] = build(v, M)
+            kw[k] = build(v, M, shared)
         elif isinstance(v, dict):
             kw[k] = materialize_array(v)
         elif k == "inputs":
-            kw[k] = [build(s, M) for s in v]
+            kw[k] = [build(s, M, shared) for s in v]
         else:
             kw[k] = v
     E = M["extent"].ExtendMode
@@ -181,6 +192,10 @@ def build(spec, M):
         return M["cache_pe"].CachePE(kw["source"])
     if kind == "TransformPE":
         return M["transform_pe"].TransformPE(kw["source"], func=numpy_func(kw["ops"]), name="ops")
+    if kind == "KarplusStrongPE":
+        return M["karplus_strong_pe"].KarplusStrongPE(**kw)
+    if kind == "AnalogOscPE":
+        return M["analog_osc_pe"].AnalogOscPE(**kw)
     raise KeyError(kind)
 
 

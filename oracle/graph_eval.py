@@ -5,7 +5,10 @@ Evaluates a golden-case SPEC (see oracle/golden_cases.py) on the CPU by composin
 oracle functions of oracle/pe_oracle.py with the reference's pull semantics: every
 node renders exactly `n` frames for (start, n); MixPE skips inputs whose extent
 misses the window (mix_pe.py:81-85); windowing nodes zero-fill / hold outside their
-extent.  This is glue only -- all arithmetic lives in pe_oracle.py.
+extent.  This is glue only -- all arithmetic lives in pe_oracle.py and sources_oracle.py.
+
+A node that carries `"share": <name>` is ONE instance wherever that name appears in the case's graph (every occurrence
+repeats the same spec): how a graph pulls one PE from two places, e.g. MixPE(c, GainPE(c)) over a CachePE c.
 """
 
 from __future__ import annotations
@@ -14,6 +17,7 @@ import numpy as np
 
 from . import pe_oracle as O
 from .golden_cases import materialize_array
+from .sources_oracle import AnalogOsc, KarplusStrong
 
 INF = (None, None)
 
@@ -55,30 +59,45 @@ def _intersects(a, b):
     return True
 
 
+def make_node(spec, sr, shared=None):
+    """Node(spec), or the node already made for its `share` name."""
+    shared = {} if shared is None else shared
+    name = spec.get("share")
+    if name is None:
+        return Node(spec, sr, shared)
+    if name not in shared:
+        shared[name] = Node(spec, sr, shared)
+    return shared[name]
+
+
 class Node:
-    def __init__(self, spec, sr):
+    def __init__(self, spec, sr, shared=None):
+        shared = {} if shared is None else shared
+        self._shared = shared
         self.spec = spec
         self.sr = sr
         self.kind = spec["pe"]
-        self.kw = {k: v for k, v in spec.items() if k != "pe"}
+        self.kw = {k: v for k, v in spec.items() if k not in ("pe", "share")}
         self.sub = {}
         for k, v in self.kw.items():
             if isinstance(v, dict) and "pe" in v:
-                self.sub[k] = Node(v, sr)
+                self.sub[k] = make_node(v, sr, shared)
             elif k == "inputs":
-                self.sub[k] = [Node(s, sr) for s in v]
+                self.sub[k] = [make_node(s, sr, shared) for s in v]
         if self.kind == "ArrayPE":
             self.array = materialize_array(self.kw["data"])
             if self.array.ndim == 1:
                 self.array = self.array.reshape(-1, 1)
         if self.kind in ("CompressorPE", "LimiterPE", "ExpanderPE"):
             self._build_dynamics_processor()
+        self.ks = self.osc = None
+        self.osc_edge = np.inf      # AnalogOscPE (stateful): closest approach of a phase to a waveform edge so far
         self.reset()
 
     def _build_dynamics_processor(self):
         """compressor_pe.py:121-161, 237-259, 293-326: CachePE(source) feeds an EnvelopePE and a DynamicsPE."""
         kw = self.kw
-        cache = Node({"pe": "CachePE", "source": self.spec["source"]}, self.sr)
+        cache = Node({"pe": "CachePE", "source": self.spec["source"]}, self.sr, self._shared)
         if self.kind == "ExpanderPE":
             env = {"pe": "EnvelopePE", "attack": kw.get("attack", 0.001), "release": kw.get("release", 0.05),
                    "mode": "peak"}
@@ -138,6 +157,15 @@ class Node:
             self.state = O.convolve_state()
         elif k == "TriggerRestartPE":
             self.state = {"t0": None}
+        elif k == "KarplusStrongPE":
+            # reset_state() drops the line: the next render draws the excitation again (karplus_strong_pe.py:132-133)
+            self.ks = KarplusStrong(self.sr, kw["frequency"], kw.get("rho", 0.996), kw.get("duration"),
+                                    kw.get("rho_damping"), kw.get("amplitude", 0.3), kw.get("seed"),
+                                    int(kw.get("channels", 1)))
+        elif k == "AnalogOscPE":
+            # phase 0, saw value -1, no last render end (analog_osc_pe.py:102-105)
+            pure = not any(x in self.sub for x in ("frequency", "duty_cycle"))
+            self.osc = AnalogOsc(self.sr, str(kw.get("waveform", "rectangle")).lower(), pure)
         elif k == "SpatialPE" and kw["method"] == "hrtf":
             self.state = getattr(self, "state", None) or O.hrtf_state()     # survives start() like the reference's
         if not recursive:
@@ -149,7 +177,8 @@ class Node:
     # ------------------------------------------------------------------ static info
     def channels(self):
         k, kw = self.kind, self.kw
-        if k in ("ConstantPE", "IdentityPE", "DiracPE", "SinePE", "BlitSawPE", "SuperSawPE"):
+        if k in ("ConstantPE", "IdentityPE", "DiracPE", "SinePE", "BlitSawPE", "SuperSawPE", "KarplusStrongPE",
+                 "AnalogOscPE"):
             return int(kw.get("channels", 1))
         if k == "ArrayPE":
             return self.array.shape[1]
@@ -242,7 +271,9 @@ class Node:
             return self.sub["source"].extent()
         if k in ("TransformPE", "EnvelopePE", "SpatialPE"):
             return self.sub["source"].extent()       # transform_pe.py:92-94, envelope_pe.py:104-106, spatial_pe.py:638-640
-        if k in ("SinePE", "BlitSawPE", "SuperSawPE", "PeriodicGate"):
+        if k == "KarplusStrongPE":
+            return (0, None)
+        if k in ("SinePE", "BlitSawPE", "SuperSawPE", "PeriodicGate", "AnalogOscPE"):
             ext = INF
             for name in ("frequency", "amplitude", "phase", "m", "duty_cycle"):
                 if name in self.sub:
@@ -405,6 +436,18 @@ class Node:
                 info = wav_io.read_info(path)
                 self.state["ir"] = O.pcm16_to_float(wav_io.read_frames(path, info, 0, info.frames))
             return O.spatial_hrtf(self.state, x, start, self.state["ir"], float(kw["azimuth"]))
+        if k == "KarplusStrongPE":
+            return self.ks.render(start, n)
+        if k == "AnalogOscPE":
+            # the parameter streams widened to float64 (analog_osc_pe.py:182-183), one float32 rounding on output
+            f = self._param("frequency", start, n, 440.0)
+            d = self._param("duty_cycle", start, n, 0.5)
+            f = f[:, 0].astype(np.float64) if isinstance(f, np.ndarray) else np.full(n, float(f))
+            d = d[:, 0].astype(np.float64) if isinstance(d, np.ndarray) else np.full(n, float(d))
+            y = self.osc.render(start, f, d).astype(np.float32)
+            if not self.osc.pure:
+                self.osc_edge = min(self.osc_edge, self.osc.edge_distance())
+            return np.repeat(y[:, None], int(kw.get("channels", 1)), axis=1)
         if k == "ConvolvePE":
             if "h" not in self.state:
                 L = self.sub["fir"].extent()[1]
@@ -524,5 +567,5 @@ class Node:
 
 def run_case(case):
     """Render every block of a golden case through the oracle; returns list of arrays."""
-    g = Node(case["graph"], case["sr"])
+    g = make_node(case["graph"], case["sr"])
     return [g.render(int(s), int(n)) for s, n in case["blocks"]]

@@ -1,5 +1,6 @@
 """Build a pygmu2_amd PE graph (the HIP product path) from a golden-case SPEC
-(see oracle/golden_cases.py for the format)."""
+(see oracle/golden_cases.py for the format; a node with `"share": <name>` is one instance wherever
+the name appears, as in oracle/graph_eval.py)."""
 
 import pygmu2_amd as pg
 from oracle.golden_cases import materialize_array
@@ -10,21 +11,33 @@ _SIMPLE = {
     "BlitSawPE": pg.BlitSawPE, "SuperSawPE": pg.SuperSawPE, "CombPE": pg.CombPE,
     "AdsrGatedPE": pg.AdsrGatedPE, "AdsrTriggeredPE": pg.AdsrTriggeredPE,
     "PeriodicGate": pg.PeriodicGate, "PeriodicTrigger": pg.PeriodicTrigger,
+    "KarplusStrongPE": pg.KarplusStrongPE, "AnalogOscPE": pg.AnalogOscPE,
 }
 
 
-def build(spec):
+def build(spec, shared=None):
+    shared = {} if shared is None else shared
+    name = spec.get("share")
+    if name is not None and name in shared:
+        return shared[name]
+    pe = _build(spec, shared)
+    if name is not None:
+        shared[name] = pe
+    return pe
+
+
+def _build(spec, shared):
     kind = spec["pe"]
     kw = {}
     for k, v in spec.items():
-        if k == "pe":
+        if k in ("pe", "share"):
             continue
         if isinstance(v, dict) and "pe" in v:
-            kw[k] = build(v)
+            kw[k] = build(v, shared)
         elif isinstance(v, dict):
             kw[k] = materialize_array(v)
         elif k == "inputs":
-            kw[k] = [build(s) for s in v]
+            kw[k] = [build(s, shared) for s in v]
         else:
             kw[k] = v
     if "extend_mode" in kw:

@@ -188,6 +188,13 @@ def _graph(seed):
             "keep": list(range(len(blocks)))}
 
 
+def _bit_exact(graph) -> bool:
+    """A graph built only from kinds DESIGN section 6 holds bit-exact must match the oracle exactly
+    (fuzz_graphs_all.bit_exact keeps the list)."""
+    from fuzz_graphs_all import bit_exact
+    return bit_exact(graph)
+
+
 def _where_the_reference_is_finite(g, w):
     """EnvelopePE(mode=RMS): scipy's running-sum uniform_filter1d can drift a hair below zero after a loud passage, and
     the reference then takes sqrt(negative) = NaN (envelope_pe.py:208-225) -- which every stateful PE downstream keeps
@@ -207,9 +214,13 @@ def test_random_graph_matches_oracle(seed):
     case = _graph(seed)
     got = hip_run(case)
     want = oracle_run(case)
+    exact = _bit_exact(case["graph"])
     for i, (g, w) in enumerate(zip(got, want)):
         assert g.shape == w.shape, (case, i, g.shape, w.shape)
         assert np.all(np.isfinite(g)), (case["graph"], i)
+        if exact:
+            assert np.array_equal(g, w), (case["graph"], case["blocks"], i, "bit-exact graph", int(np.count_nonzero(g != w)))
+            continue
         g, w = _where_the_reference_is_finite(g, w)
         peak = float(np.max(np.abs(w))) if w.size else 0.0
         err = float(np.max(np.abs(g.astype(np.float64) - w.astype(np.float64)))) if w.size else 0.0
@@ -237,9 +248,13 @@ def test_random_graph_long_blocks(seed):
         # when its input is scaled by 1 + 1e-7: a chaotic orbit, which only bit-identical tanh could follow for 1e5 samples)
         pytest.skip("a ladder at or above self-oscillation: the reference itself is ill-conditioned over long blocks")
     got = hip_run(case)
+    exact = _bit_exact(case["graph"])
     for i, (g, w) in enumerate(zip(got, want)):
         assert g.shape == w.shape, (case, i, g.shape, w.shape)
         assert np.all(np.isfinite(g)), (case["graph"], i)
+        if exact:
+            assert np.array_equal(g, w), (case["graph"], case["blocks"], i, "bit-exact graph", int(np.count_nonzero(g != w)))
+            continue
         g, w = _where_the_reference_is_finite(g, w)
         peak = float(np.max(np.abs(w))) if w.size else 0.0
         err = float(np.max(np.abs(g.astype(np.float64) - w.astype(np.float64)))) if w.size else 0.0
@@ -274,9 +289,13 @@ def test_random_graph_streams(seed):
     if _has_self_oscillating_ladder(case["graph"], case["sr"]) and _reference_is_ill_conditioned(case, want):
         pytest.skip("a ladder at or above self-oscillation: the reference itself is ill-conditioned over long streams")
     got = hip_run(case)
+    exact = _bit_exact(case["graph"])
     for i, (g, w) in enumerate(zip(got, want)):
         assert g.shape == w.shape, (case, i, g.shape, w.shape)
         assert np.all(np.isfinite(g)), (case["graph"], i)
+        if exact:
+            assert np.array_equal(g, w), (case["graph"], case["blocks"], i, "bit-exact graph", int(np.count_nonzero(g != w)))
+            continue
         g, w = _where_the_reference_is_finite(g, w)
         peak = float(np.max(np.abs(w))) if w.size else 0.0
         err = float(np.max(np.abs(g.astype(np.float64) - w.astype(np.float64)))) if w.size else 0.0
