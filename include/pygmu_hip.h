@@ -292,6 +292,37 @@ int pgx_interp_lookup(float *out, const float *window, int64_t window_start, int
 /* result_dev[0..1] = min, max of float64(start + i) - delay[i]  (np.min / np.max of the indices,
  * interpolated_lookup.py:111-112): the host sizes the source window from them. */
 int pgx_index_range(double *result_dev, const float *delay, int64_t start, int64_t n);
+/* ------------------------------------------------------------------ WavetablePE / TimeWarpPE
+ * The two other callers of interpolated_lookup, through the same device function as pgx_interp_lookup.
+ *
+ * WavetablePE._render (wavetable_pe.py:117-169) in one launch: index = float64(indexer[i]) put through the
+ * out-of-bounds rule (:146-159), then linear / Catmull-Rom interpolation over the rendered table window
+ * [window_start, window_start + window_len), neighbours clipped to it.  oob_mode 0 zero, 1 clamp, 2 wrap; with
+ * finite == 0 (a table without a finite extent) the index stays raw in every mode and nothing is masked.
+ *   wrap : ((raw - wt_start) % wt_len) + wt_start with numpy's float remainder (fmod, + wt_len if negative);
+ *          an index in (wt_end - 1, wt_end) interpolates towards the frame at wt_end, as the reference does
+ *   clamp: clip to [wt_start, wt_end - 1]
+ *   zero : raw index; 0 where raw < wt_start or raw >= wt_end
+ * A window of at most 2560 floats is staged in LDS once per workgroup and the gathers are served from there. */
+int pgx_wavetable(float *out, const float *indexer, int64_t n, const float *window, int64_t window_start,
+                  int64_t window_len, int channels, int cubic, int oob_mode, int finite, double wt_start,
+                  double wt_end);
+/* result_dev[0..1] = min, max of those processed indices (np.min / np.max, interpolated_lookup.py:126-127) for a
+ * table whose window is not kept on the device: the host sizes the table render from them. */
+int pgx_wavetable_range(double *result_dev, const float *indexer, int64_t n, int oob_mode, int finite,
+                        double wt_start, double wt_end);
+/* TimeWarpPE._render with a PE rate, index side (timewarp_pe.py:150-163): positions[i] = state[0] +
+ * sum(rate[0..i)) (np.cumsum; here a float64 scan over workgroup segments), range_dev[0..1] = min, max of the
+ * positions, then state[0] += sum(rate).  workspace: PGX_TIMEWARP_WORKSPACE_DOUBLES doubles of scratch. */
+#define PGX_TIMEWARP_WORKSPACE_DOUBLES 768
+int pgx_timewarp_scan(double *positions, double *range_dev, double *state, double *workspace, const float *rate,
+                      int64_t n);
+/* TimeWarpPE._render, lookup side (timewarp_pe.py:165-184): interpolation at positions[i], or at
+ * pos0 + i * rate when positions is NULL (a scalar rate needs no stream and no scan); 0 where the position is
+ * below extent_start (has_start) or at / beyond extent_end (has_end). */
+int pgx_timewarp(float *out, int64_t n, const double *positions, double pos0, double rate, const float *window,
+                 int64_t window_start, int64_t window_len, int channels, int cubic, int has_start,
+                 double extent_start, int has_end, double extent_end);
 /* partials_dev[2 p + {0, 1}] = (min, max) of workgroup p's share of the mono stream x[0..n), p < parts <= 1024
  * (NaN if it met one): the host folds the pairs.  LadderPE with a PE-driven cutoff / resonance sizes the warm-up
  * of its time segments from the block's lowest cutoff and highest resonance (ladder_pe.py:84-113 clamps). */

@@ -6,8 +6,8 @@ ProcessingElement / SourcePE / Snippet / Extent / Renderer / NullRenderer and th
 SinePE, BlitSawPE, SuperSawPE, BiquadPE, LadderPE, CombPE, MixPE, GainPE, ConvolvePE,
 AdsrGatedPE, AdsrTriggeredPE, PeriodicGate, PeriodicTrigger, ConstantPE, ArrayPE,
 DiracPE, IdentityPE, CachePE, CropPE, SVFilterPE, EnvelopePE, TransformPE, DelayPE, PiecewisePE,
-TriggerRestartPE, ReverbPE, WavWriterPE, WavReaderPE, KarplusStrongPE, AnalogOscPE (+ render_to_file,
-rho_for_decay_db).  Snippet payloads live in HBM; all DSP runs in
+TriggerRestartPE, ReverbPE, WavWriterPE, WavReaderPE, KarplusStrongPE, AnalogOscPE, WavetablePE, TimeWarpPE
+(+ render_to_file, rho_for_decay_db).  Snippet payloads live in HBM; all DSP runs in
 hand-written HIP kernels for gfx950 behind the C ABI of include/pygmu_hip.h.
 """
 
@@ -57,6 +57,11 @@ from .wav_writer_pe import WavWriterPE
 from .wav_reader_pe import WavReaderPE
 from .karplus_strong_pe import KarplusStrongPE, rho_for_decay_db
 from .analog_osc_pe import AnalogOscPE
+# WavetablePE and TimeWarpPE are bound here (pg.WavetablePE works) but are NOT in __all__ yet: every PE named there
+# must have fuzz-corpus cases and a graph-oracle evaluator under oracle/ (tests/test_oracle_fuzz_golden.py), and those
+# arrive with the change that enters the two classes into that census.  tests/test_gpu_playback_fuzz.py stands in.
+from .wavetable_pe import OutOfBoundsMode, WavetablePE
+from .timewarp_pe import TimeWarpPE
 from .utils import render_to_file
 from . import device, diagnostics
 
@@ -71,5 +76,5 @@ __all__ = [
     "ReverbPE", "SpatialPE", "SpatialMethod", "SpatialAdapter", "SpatialLinear", "SpatialConstantPower",
     "SpatialHRTF", "LoopPE", "WindowMode", "WindowPE", "DynamicsMode", "DynamicsPE", "CompressorPE", "LimiterPE",
     "ExpanderPE", "db_to_ratio", "ratio_to_db", "WavWriterPE", "WavReaderPE", "render_to_file", "device", "diagnostics",
-    "KarplusStrongPE", "rho_for_decay_db", "AnalogOscPE",
+    "KarplusStrongPE", "rho_for_decay_db", "AnalogOscPE", "OutOfBoundsMode",
 ]

@@ -238,6 +238,33 @@ __device__ __forceinline__ void pgx_sincos(double x, double &sn, double &cs) {
     sn = (qi & 1) ? -a : a;
     cs = (qi & 1) ? -b : b;
 }
+
+// Block-wide exclusive prefix sum of one double per thread (sequential-in-lane order), plus the block total, for a
+// workgroup of WAVES wave64s.  `lds` must hold WAVES doubles.  Contains two __syncthreads.
+template <int WAVES>
+__device__ __forceinline__ double block_excl_sum(double v, double *lds, double &total) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    double inc = v;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        double o = __shfl_up(inc, d, 64);
+        if (lane >= d) inc = o + inc;
+    }
+    if (lane == 63) lds[wave] = inc;
+    __syncthreads();
+    double woff = 0.0, tot = 0.0;
+#pragma unroll
+    for (int w = 0; w < WAVES; ++w) {
+        double t = lds[w];
+        if (w < wave) woff = woff + t;
+        tot = tot + t;
+    }
+    __syncthreads();
+    total = tot;
+    double ex = __shfl_up(inc, 1, 64);
+    if (lane == 0) ex = 0.0;
+    return woff + ex;
+}
 #endif
 
 // Grid size for a grid-stride elementwise kernel: a workgroup per `block` items, at most 128 per CU (PGX_GRID_CAP).

@@ -10,11 +10,52 @@ namespace {
 
 constexpr int kBlock = 256;
 
+__device__ __forceinline__ double block_excl_sum(double v, double *lds, double &total) {
+    return pgx::block_excl_sum<kBlock / 64>(v, lds, total);
+}
+
 // ------------------------------------------------------------------------------------------------
 // DelayPE / interpolated_lookup (interpolated_lookup.py:28-77, delay_pe.py:170-216)
 //   index = float64(start + i) - delay[i];  floor, fraction, clipped neighbours of the rendered
 //   source window [win_start, win_start + win_len); out-of-extent indices -> 0.
 // ------------------------------------------------------------------------------------------------
+// One output frame of _linear_interp / _cubic_interp (interpolated_lookup.py:33-87) at the fractional `index` over the
+// window [win_start, win_start + win_len) -- in HBM or staged in LDS: every caller of interpolated_lookup (DelayPE,
+// WavetablePE, TimeWarpPE) interpolates through this one function.
+__device__ __forceinline__ void interp_at(float *o, const float *win, int64_t win_start, int64_t win_len, int channels,
+                                          double index, int cubic, bool oob) {
+    const double fl = floor(index);
+    const double t = index - fl;
+    const int64_t p1 = (int64_t)fl - win_start;
+    const int64_t last = win_len - 1;
+    auto clip = [last](int64_t v) { return v < 0 ? 0 : (v > last ? last : v); };
+    if (!cubic) {
+        const float *a = win + clip(p1) * channels;
+        const float *b = win + clip(p1 + 1) * channels;
+        for (int c = 0; c < channels; ++c) {
+            const double v = (1.0 - t) * (double)a[c] + t * (double)b[c];
+            o[c] = oob ? 0.0f : (float)v;
+        }
+    } else {
+        const float *q0 = win + clip(p1 - 1) * channels;
+        const float *q1 = win + clip(p1) * channels;
+        const float *q2 = win + clip(p1 + 1) * channels;
+        const float *q3 = win + clip(p1 + 2) * channels;
+        const double t2 = t * t;
+        const double t3 = t2 * t;
+        for (int c = 0; c < channels; ++c) {
+            const float p0 = q0[c], pa = q1[c], pb = q2[c], pc = q3[c];
+            // float32 sub-expressions, exactly as numpy evaluates `2.0 * p1`, `-p0 + p2`, ... on float32 arrays
+            const float k0 = 2.0f * pa;
+            const float k1 = -p0 + pb;
+            const float k2 = ((2.0f * p0 - 5.0f * pa) + 4.0f * pb) - pc;
+            const float k3 = ((-p0 + 3.0f * pa) - 3.0f * pb) + pc;
+            const double v = 0.5 * ((((double)k0 + (double)k1 * t) + (double)k2 * t2) + (double)k3 * t3);
+            o[c] = oob ? 0.0f : (float)v;
+        }
+    }
+}
+
 __global__ void __launch_bounds__(kBlock)
 k_interp_lookup(float *out, const float *win, int64_t win_start, int64_t win_len, int channels, int64_t start,
                 int64_t n, double delay_scalar, const float *delay, int cubic, int bounded, double ext_start,
@@ -22,37 +63,8 @@ k_interp_lookup(float *out, const float *win, int64_t win_start, int64_t win_len
     const int64_t stride = (int64_t)gridDim.x * kBlock;
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
         const double index = (double)(start + i) - (delay ? (double)delay[i] : delay_scalar);
-        const double fl = floor(index);
-        const double t = index - fl;
-        const int64_t p1 = (int64_t)fl - win_start;
         const bool oob = bounded && (index < ext_start || index >= ext_end);
-        const int64_t last = win_len - 1;
-        auto clip = [last](int64_t v) { return v < 0 ? 0 : (v > last ? last : v); };
-        if (!cubic) {
-            const float *a = win + clip(p1) * channels;
-            const float *b = win + clip(p1 + 1) * channels;
-            for (int c = 0; c < channels; ++c) {
-                const double v = (1.0 - t) * (double)a[c] + t * (double)b[c];
-                out[i * channels + c] = oob ? 0.0f : (float)v;
-            }
-        } else {
-            const float *q0 = win + clip(p1 - 1) * channels;
-            const float *q1 = win + clip(p1) * channels;
-            const float *q2 = win + clip(p1 + 1) * channels;
-            const float *q3 = win + clip(p1 + 2) * channels;
-            const double t2 = t * t;
-            const double t3 = t2 * t;
-            for (int c = 0; c < channels; ++c) {
-                const float p0 = q0[c], pa = q1[c], pb = q2[c], pc = q3[c];
-                // float32 sub-expressions, exactly as numpy evaluates `2.0 * p1`, `-p0 + p2`, ... on float32 arrays
-                const float k0 = 2.0f * pa;
-                const float k1 = -p0 + pb;
-                const float k2 = ((2.0f * p0 - 5.0f * pa) + 4.0f * pb) - pc;
-                const float k3 = ((-p0 + 3.0f * pa) - 3.0f * pb) + pc;
-                const double v = 0.5 * ((((double)k0 + (double)k1 * t) + (double)k2 * t2) + (double)k3 * t3);
-                out[i * channels + c] = oob ? 0.0f : (float)v;
-            }
-        }
+        interp_at(out + i * channels, win, win_start, win_len, channels, index, cubic, oob);
     }
 }
 
@@ -112,6 +124,209 @@ k_stream_range(double *partials, const float *x, int64_t n) {
     if (threadIdx.x == 0) {
         partials[blockIdx.x * 2 + 0] = smin[0];
         partials[blockIdx.x * 2 + 1] = smax[0];
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// WavetablePE (wavetable_pe.py:117-169): out[i] = table[indexer[i]], the index put through the out-of-bounds rule
+// first.  mode: 0 zero, 1 clamp, 2 wrap; `finite` == 0 (an unbounded table) leaves the index raw in every mode.
+// ------------------------------------------------------------------------------------------------
+// The window is staged in LDS up to this size (10 KiB of a CU's 160: LDS never limits the waves on a CU) -- a 2048-frame
+// mono table with its guard frames.  Measured per launch (tools/playback_probe.py, profiles/r5_playback_probe.md), staged
+// against gathered from global memory: 2 051 floats 6.4 vs 6.9 us at 1 M frames, 4.4 vs 4.4 at 48 000; 4 003 floats 7.2
+// vs 7.8 (random indices) but 7.2 vs 6.8 (saw) at 1 M and 5.4 vs 4.4 at 48 000; 8 003 floats slower everywhere (8.7 vs
+// 4.4 at 48 000): a table this small lives in the caches anyway, and what staging costs is a grid of few, long workgroups.
+constexpr int kWtLdsFloats = 2560;
+constexpr int kWtLdsMaxFloats = 16384;    // 64 KiB: the most a launch may ask for (PGX_WT_LDS_FLOATS)
+
+__device__ __forceinline__ double wt_index(double raw, int mode, int finite, double wt_start, double wt_end, bool &oob) {
+    oob = false;
+    if (!finite) return raw;
+    if (mode == 2) {
+        // numpy's float `%`: fmod (exact), then the divisor's sign
+        const double len = wt_end - wt_start;
+        double m = fmod(raw - wt_start, len);
+        if (m != 0.0) {
+            if (m < 0.0) m += len;
+        } else {
+            m = copysign(0.0, len);
+        }
+        return m + wt_start;
+    }
+    if (mode == 1) {
+        const double hi = wt_end - 1.0;                      // np.clip: NaN stays NaN
+        return raw < wt_start ? wt_start : (raw > hi ? hi : raw);
+    }
+    oob = raw < wt_start || raw >= wt_end;
+    return raw;
+}
+
+// `staged` != 0: the window (kWtLdsFloats floats by default) is copied to LDS once per workgroup and every gather is served
+// from there; the grid is sized so that each workgroup has at least as many gathers to make as floats to stage.
+__global__ void __launch_bounds__(kBlock)
+k_wavetable(float *out, const float *indexer, int64_t n, const float *win, int64_t win_start, int64_t win_len,
+            int channels, int cubic, int mode, int finite, double wt_start, double wt_end, int staged) {
+    extern __shared__ float tab[];
+    if (staged) {
+        const int m = (int)(win_len * channels);
+        for (int k = threadIdx.x; k < m; k += kBlock) tab[k] = win[k];
+        __syncthreads();
+    }
+    const int64_t stride = (int64_t)gridDim.x * kBlock;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
+        bool oob;
+        const double index = wt_index((double)indexer[i], mode, finite, wt_start, wt_end, oob);
+        if (staged) interp_at(out + i * channels, tab, win_start, win_len, channels, index, cubic, oob);
+        else interp_at(out + i * channels, win, win_start, win_len, channels, index, cubic, oob);
+    }
+}
+
+// NaN-propagating min / max of one value per thread over the workgroup -> (lo, hi) on thread 0
+__device__ __forceinline__ void block_range(double &lo, double &hi, double *smin, double *smax) {
+    smin[threadIdx.x] = lo;
+    smax[threadIdx.x] = hi;
+    __syncthreads();
+    for (int s = kBlock / 2; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) {
+            const double a = smin[threadIdx.x + s], b = smax[threadIdx.x + s];
+            if (a != a || a < smin[threadIdx.x]) smin[threadIdx.x] = a;
+            if (b != b || b > smax[threadIdx.x]) smax[threadIdx.x] = b;
+        }
+        __syncthreads();
+    }
+    lo = smin[0];
+    hi = smax[0];
+    __syncthreads();
+}
+
+// min / max of the processed indices -> result[0..1] (one workgroup): the window of a table that is not kept
+__global__ void __launch_bounds__(kBlock)
+k_wavetable_range(double *result, const float *indexer, int64_t n, int mode, int finite, double wt_start,
+                  double wt_end) {
+    __shared__ double smin[kBlock], smax[kBlock];
+    double lo = INFINITY, hi = -INFINITY;
+    for (int64_t i = threadIdx.x; i < n; i += kBlock) {
+        bool oob;
+        const double index = wt_index((double)indexer[i], mode, finite, wt_start, wt_end, oob);
+        lo = fmin(lo, index);
+        hi = fmax(hi, index);
+        if (index != index) lo = hi = index;
+    }
+    block_range(lo, hi, smin, smax);
+    if (threadIdx.x == 0) {
+        result[0] = lo;
+        result[1] = hi;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// TimeWarpPE (timewarp_pe.py:147-184): positions[i] = pos + sum(rate[0..i)), pos += sum(rate).
+// The float64 prefix sum runs over segments of kTwTile-frame tiles, one workgroup per segment:
+//   k_tw_reduce     each segment's sum of rates -> partials[seg]                  (skipped for one segment)
+//   k_tw_positions  offset = partials before the segment, in order; block_excl_sum per tile; positions and the
+//                   segment's min / max                                           (one segment: also the finish)
+//   k_tw_finish     range[0..1] = min / max over the segments; state[0] += sum(partials)
+// ------------------------------------------------------------------------------------------------
+constexpr int kTwT = 8;
+constexpr int kTwTile = kBlock * kTwT;
+constexpr int kTwMaxSeg = PGX_TIMEWARP_WORKSPACE_DOUBLES / 3;
+
+__global__ void __launch_bounds__(kBlock)
+k_tw_reduce(double *partials, const float *rate, int64_t n, int64_t seg_frames) {
+    __shared__ double lds[kBlock / 64];
+    const int64_t first = (int64_t)blockIdx.x * seg_frames;
+    const int64_t end = first + seg_frames < n ? first + seg_frames : n;
+    double carry = 0.0;
+    for (int64_t base = first; base < end; base += kTwTile) {
+        const int64_t f0 = base + (int64_t)threadIdx.x * kTwT;
+        double run = 0.0;
+#pragma unroll
+        for (int j = 0; j < kTwT; ++j) run = run + ((f0 + j < end) ? (double)rate[f0 + j] : 0.0);
+        double tile_total;
+        block_excl_sum(run, lds, tile_total);
+        carry = carry + tile_total;
+    }
+    if (threadIdx.x == 0) partials[blockIdx.x] = carry;
+}
+
+__global__ void __launch_bounds__(kBlock)
+k_tw_positions(double *positions, double *segrange, double *range, double *state, const double *partials,
+               const float *rate, int64_t n, int64_t seg_frames) {
+    __shared__ double lds[kBlock / 64];
+    __shared__ double smin[kBlock], smax[kBlock];
+    const double pos = state[0];
+    double carry = 0.0;
+    for (int s = 0; s < (int)blockIdx.x; ++s) carry = carry + partials[s];
+    const int64_t first = (int64_t)blockIdx.x * seg_frames;
+    const int64_t end = first + seg_frames < n ? first + seg_frames : n;
+    double lo = INFINITY, hi = -INFINITY;
+    for (int64_t base = first; base < end; base += kTwTile) {
+        const int64_t f0 = base + (int64_t)threadIdx.x * kTwT;
+        double before[kTwT];
+        double run = 0.0;
+#pragma unroll
+        for (int j = 0; j < kTwT; ++j) {
+            before[j] = run;
+            run = run + ((f0 + j < end) ? (double)rate[f0 + j] : 0.0);
+        }
+        double tile_total;
+        const double off = carry + block_excl_sum(run, lds, tile_total);
+        carry = carry + tile_total;
+#pragma unroll
+        for (int j = 0; j < kTwT; ++j) {
+            if (f0 + j < end) {
+                const double p = pos + (off + before[j]);
+                positions[f0 + j] = p;
+                lo = fmin(lo, p);
+                hi = fmax(hi, p);
+                if (p != p) lo = hi = p;
+            }
+        }
+    }
+    block_range(lo, hi, smin, smax);
+    if (threadIdx.x == 0) {
+        if (gridDim.x == 1) {
+            range[0] = lo;
+            range[1] = hi;
+            state[0] = pos + carry;
+        } else {
+            segrange[2 * blockIdx.x + 0] = lo;
+            segrange[2 * blockIdx.x + 1] = hi;
+        }
+    }
+}
+
+__global__ void __launch_bounds__(kBlock)
+k_tw_finish(double *range, double *state, const double *partials, const double *segrange, int nseg) {
+    __shared__ double smin[kBlock], smax[kBlock];
+    double lo = INFINITY, hi = -INFINITY;
+    for (int s = threadIdx.x; s < nseg; s += kBlock) {
+        const double a = segrange[2 * s], b = segrange[2 * s + 1];
+        if (a != a || a < lo) lo = a;
+        if (b != b || b > hi) hi = b;
+        if (a != a || b != b) lo = hi = NAN;
+    }
+    block_range(lo, hi, smin, smax);
+    if (threadIdx.x == 0) {
+        range[0] = lo;
+        range[1] = hi;
+        double total = 0.0;
+        for (int s = 0; s < nseg; ++s) total = total + partials[s];
+        state[0] = state[0] + total;
+    }
+}
+
+// The read itself: index = positions[i], or pos0 + i * rate for a scalar rate; 0 outside the source's extent, either
+// side of which may be open (timewarp_pe.py:165-175).
+__global__ void __launch_bounds__(kBlock)
+k_timewarp(float *out, int64_t n, const double *positions, double pos0, double rate, const float *win,
+           int64_t win_start, int64_t win_len, int channels, int cubic, int has_start, double ext_start, int has_end,
+           double ext_end) {
+    const int64_t stride = (int64_t)gridDim.x * kBlock;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
+        const double index = positions ? positions[i] : pos0 + (double)i * rate;
+        const bool oob = (has_start && index < ext_start) || (has_end && index >= ext_end);
+        interp_at(out + i * channels, win, win_start, win_len, channels, index, cubic, oob);
     }
 }
 
@@ -306,6 +521,82 @@ int pgx_interp_lookup(float *out, const float *window, int64_t window_start, int
                        window_start, window_len, channels, start, n, delay_scalar, delay, cubic, bounded,
                        extent_start, extent_end);
     PGX_LAUNCH_CHECK("k_interp_lookup");
+    return PGX_OK;
+}
+
+int pgx_wavetable(float *out, const float *indexer, int64_t n, const float *window, int64_t window_start,
+                  int64_t window_len, int channels, int cubic, int oob_mode, int finite, double wt_start,
+                  double wt_end) {
+    PGX_REQUIRE_INIT();
+    if (n <= 0) return PGX_OK;
+    PGX_CHECK_ARG(out && indexer && window && window_len >= 1 && channels >= 1 && oob_mode >= 0 && oob_mode <= 2,
+                  "pgx_wavetable: bad argument");
+    const int64_t floats = window_len * channels;
+    const int taps = cubic ? 4 : 2;
+    int grid = pgx::grid_for(n, kBlock);
+    int staged = 0;
+    // PGX_WT_LDS_FLOATS (experiments, tools/playback_probe.py): another staging limit; 0 gathers from global memory
+    const char *lds_env = getenv("PGX_WT_LDS_FLOATS");
+    int64_t lds_floats = lds_env ? atoi(lds_env) : kWtLdsFloats;
+    if (lds_floats > kWtLdsMaxFloats) lds_floats = kWtLdsMaxFloats;
+    if (floats <= lds_floats && n * taps * channels >= floats) {
+        // a workgroup stages the whole window: give each one at least as many gathers as that costs
+        staged = 1;
+        const int64_t per_group = pgx::ceil_div(floats, (int64_t)taps * channels);
+        const int64_t groups = n / (per_group > kBlock ? per_group : kBlock);
+        if (groups < grid) grid = groups < 1 ? 1 : (int)groups;
+    }
+    hipLaunchKernelGGL(k_wavetable, dim3(grid), dim3(kBlock), staged ? (size_t)floats * sizeof(float) : 0,
+                       pgx::stream(), out, indexer, n, window, window_start, window_len, channels, cubic ? 1 : 0,
+                       oob_mode, finite ? 1 : 0, wt_start, wt_end, staged);
+    PGX_LAUNCH_CHECK("k_wavetable");
+    return PGX_OK;
+}
+
+int pgx_wavetable_range(double *result_dev, const float *indexer, int64_t n, int oob_mode, int finite, double wt_start,
+                        double wt_end) {
+    PGX_REQUIRE_INIT();
+    PGX_CHECK_ARG(result_dev && indexer && n >= 1 && oob_mode >= 0 && oob_mode <= 2, "pgx_wavetable_range: bad argument");
+    hipLaunchKernelGGL(k_wavetable_range, dim3(1), dim3(kBlock), 0, pgx::stream(), result_dev, indexer, n, oob_mode,
+                       finite ? 1 : 0, wt_start, wt_end);
+    PGX_LAUNCH_CHECK("k_wavetable_range");
+    return PGX_OK;
+}
+
+int pgx_timewarp_scan(double *positions, double *range_dev, double *state, double *workspace, const float *rate,
+                      int64_t n) {
+    PGX_REQUIRE_INIT();
+    PGX_CHECK_ARG(positions && range_dev && state && workspace && rate && n >= 1, "pgx_timewarp_scan: bad argument");
+    const int64_t tiles = pgx::ceil_div(n, kTwTile);
+    const int64_t tiles_per_seg = pgx::ceil_div(tiles, kTwMaxSeg);
+    const int64_t seg_frames = tiles_per_seg * kTwTile;
+    const int nseg = (int)pgx::ceil_div(tiles, tiles_per_seg);
+    double *partials = workspace, *segrange = workspace + kTwMaxSeg;
+    if (nseg > 1) {
+        hipLaunchKernelGGL(k_tw_reduce, dim3(nseg), dim3(kBlock), 0, pgx::stream(), partials, rate, n, seg_frames);
+        PGX_LAUNCH_CHECK("k_tw_reduce");
+    }
+    hipLaunchKernelGGL(k_tw_positions, dim3(nseg), dim3(kBlock), 0, pgx::stream(), positions, segrange, range_dev,
+                       state, partials, rate, n, seg_frames);
+    PGX_LAUNCH_CHECK("k_tw_positions");
+    if (nseg > 1) {
+        hipLaunchKernelGGL(k_tw_finish, dim3(1), dim3(kBlock), 0, pgx::stream(), range_dev, state, partials, segrange,
+                           nseg);
+        PGX_LAUNCH_CHECK("k_tw_finish");
+    }
+    return PGX_OK;
+}
+
+int pgx_timewarp(float *out, int64_t n, const double *positions, double pos0, double rate, const float *window,
+                 int64_t window_start, int64_t window_len, int channels, int cubic, int has_start,
+                 double extent_start, int has_end, double extent_end) {
+    PGX_REQUIRE_INIT();
+    if (n <= 0) return PGX_OK;
+    PGX_CHECK_ARG(out && window && window_len >= 1 && channels >= 1, "pgx_timewarp: bad argument");
+    hipLaunchKernelGGL(k_timewarp, dim3(pgx::grid_for(n, kBlock)), dim3(kBlock), 0, pgx::stream(), out, n, positions,
+                       pos0, rate, window, window_start, window_len, channels, cubic ? 1 : 0, has_start ? 1 : 0,
+                       extent_start, has_end ? 1 : 0, extent_end);
+    PGX_LAUNCH_CHECK("k_timewarp");
     return PGX_OK;
 }
 

@@ -143,30 +143,10 @@ __device__ __forceinline__ void store_frames_tiled(float *base, int64_t f0, int6
 }
 
 // ------------------------------------------------------------------------------------------------
-// Block-wide exclusive prefix sum of one double per thread (sequential-in-lane order), plus the
-// block total.  `lds` must hold kWaves doubles.  Contains two __syncthreads.
+// Block-wide exclusive prefix sum of one double per thread: pgx::block_excl_sum (pgx_common.h; TimeWarpPE's
+// position scan in pgx_lookup.hip integrates its rate with the same routine).
 __device__ __forceinline__ double block_excl_sum(double v, double *lds, double &total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    double inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        double o = __shfl_up(inc, d, 64);
-        if (lane >= d) inc = o + inc;
-    }
-    if (lane == 63) lds[wave] = inc;
-    __syncthreads();
-    double woff = 0.0, tot = 0.0;
-#pragma unroll
-    for (int w = 0; w < kWaves; ++w) {
-        double t = lds[w];
-        if (w < wave) woff = woff + t;
-        tot = tot + t;
-    }
-    __syncthreads();
-    total = tot;
-    double ex = __shfl_up(inc, 1, 64);
-    if (lane == 0) ex = 0.0;
-    return woff + ex;
+    return pgx::block_excl_sum<kWaves>(v, lds, total);
 }
 
 // Block-wide scan for the scalar constant map y' = lam^len * y + b.  On entry `e` is this thread's

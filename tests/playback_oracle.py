@@ -1,0 +1,259 @@
+"""WavetablePE / TimeWarpPE on the CPU: numpy restatements of the two `_render`s and of interpolated_lookup (the
+reference's operations in the reference's order: sequential np.cumsum for the positions, np.sum for the carried head),
+the fixture loader, and the graph builder shared by the fixture generator (tools/gen_golden_playback.py, over the
+reference's classes) and the tests (over pygmu2_amd's).
+
+Graphs are golden-case SPECs (oracle/golden_cases.py) with two more kinds:
+    {"pe": "WavetablePE", "wavetable": SPEC, "indexer": SPEC, "interpolation": "linear"|"cubic",
+     "out_of_bounds": "zero"|"clamp"|"wrap"}
+    {"pe": "TimeWarpPE", "source": SPEC, "rate": number | SPEC, "interpolation": ...}
+Every other kind is evaluated by oracle/graph_eval.py (PlaybackNode derives from its Node) and built by the caller's
+builder for the existing kinds."""
+
+from __future__ import annotations
+
+import json
+import os
+
+import numpy as np
+
+from oracle.graph_eval import INF, Node
+
+GOLDEN_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+CASES_PATH = os.path.join(GOLDEN_DIR, "playback_cases.json")
+NPZ_PATH = os.path.join(GOLDEN_DIR, "playback.npz")
+
+NEW_KINDS = ("WavetablePE", "TimeWarpPE")
+
+
+def load_cases():
+    with open(CASES_PATH) as f:
+        cases = json.load(f)
+    return cases, np.load(NPZ_PATH)
+
+
+def stored_blocks(case):
+    """Indices of the blocks whose samples the fixture keeps (every `keep_every`-th; all by default)."""
+    k = int(case.get("keep_every", 1))
+    return [i for i in range(len(case["blocks"])) if i % k == 0]
+
+
+def split_blocks(case, flat):
+    """The fixture's concatenated samples -> {block index: samples} for the stored blocks."""
+    out, at = {}, 0
+    for i in stored_blocks(case):
+        n = int(case["blocks"][i][1])
+        out[i] = flat[at:at + n]
+        at += n
+    assert at == len(flat)
+    return out
+
+
+# ---------------------------------------------------------------------------------------------- graphs
+def is_spec(v):
+    return isinstance(v, dict) and "pe" in v
+
+
+def build_graph(spec, build_existing, make_new):
+    """SPEC -> PE instance, bottom-up.  build_existing(spec) builds a node of an existing kind whose PE-valued
+    parameters are already instances (both SPEC builders pass anything that is not a SPEC through as a keyword
+    value); make_new(kind, kwargs) constructs a WavetablePE / TimeWarpPE (interpolation / out_of_bounds still strings)."""
+    node = {}
+    for k, v in spec.items():
+        if is_spec(v):
+            node[k] = build_graph(v, build_existing, make_new)
+        elif k == "inputs":
+            assert not any(_mentions_new(s) for s in v), "a MixPE input may not hold a WavetablePE / TimeWarpPE"
+            node[k] = v
+        else:
+            node[k] = v
+    if spec["pe"] in NEW_KINDS:
+        return make_new(spec["pe"], {k: v for k, v in node.items() if k != "pe"})
+    return build_existing(node)
+
+
+def _mentions_new(spec):
+    if not is_spec(spec):
+        return False
+    return spec["pe"] in NEW_KINDS or any(
+        _mentions_new(v) or (k == "inputs" and any(_mentions_new(s) for s in v)) for k, v in spec.items())
+
+
+def make_with(WavetablePE, TimeWarpPE, InterpolationMode, OutOfBoundsMode):
+    def make_new(kind, kw):
+        kw = dict(kw)
+        if "interpolation" in kw:
+            kw["interpolation"] = InterpolationMode(kw["interpolation"])
+        if kind == "WavetablePE":
+            if "out_of_bounds" in kw:
+                kw["out_of_bounds"] = OutOfBoundsMode(kw["out_of_bounds"])
+            return WavetablePE(kw.pop("wavetable"), kw.pop("indexer"), **kw)
+        return TimeWarpPE(kw.pop("source"), **kw)
+    return make_new
+
+
+# ---------------------------------------------------------------------------------------------- interpolated_lookup
+def linear_interp(indices, data, data_start):
+    """interpolated_lookup.py:33-51."""
+    idx_floor = np.floor(indices).astype(np.int64)
+    frac = (indices - idx_floor).reshape(-1, 1)
+    local_floor = idx_floor - data_start
+    lo = np.clip(local_floor, 0, len(data) - 1)
+    hi = np.clip(local_floor + 1, 0, len(data) - 1)
+    return (1.0 - frac) * data[lo] + frac * data[hi]
+
+
+def cubic_interp(indices, data, data_start):
+    """interpolated_lookup.py:54-87 (Catmull-Rom)."""
+    idx_floor = np.floor(indices).astype(np.int64)
+    t = (indices - idx_floor).reshape(-1, 1)
+    local_p1 = idx_floor - data_start
+    max_idx = len(data) - 1
+    p0 = data[np.clip(local_p1 - 1, 0, max_idx)]
+    p1 = data[np.clip(local_p1, 0, max_idx)]
+    p2 = data[np.clip(local_p1 + 1, 0, max_idx)]
+    p3 = data[np.clip(local_p1 + 2, 0, max_idx)]
+    t2 = t * t
+    t3 = t2 * t
+    return 0.5 * ((2.0 * p1) + (-p0 + p2) * t + (2.0 * p0 - 5.0 * p1 + 4.0 * p2 - p3) * t2
+                  + (-p0 + 3.0 * p1 - 3.0 * p2 + p3) * t3)
+
+
+def interpolated_lookup(render_source, indices, cubic, oob_mask=None):
+    """interpolated_lookup.py:90-144; render_source(start, n) -> float32 (n, channels)."""
+    indices = np.asarray(indices, dtype=np.float64).reshape(-1)
+    margin = 2 if cubic else 1
+    needed_min = int(np.floor(float(np.min(indices)))) - (margin - 1)
+    needed_max = int(np.ceil(float(np.max(indices)))) + margin
+    data = render_source(needed_min, needed_max - needed_min)
+    result = (cubic_interp if cubic else linear_interp)(indices, data, needed_min)
+    if oob_mask is not None and np.any(oob_mask):
+        result = result.copy()
+        result[oob_mask] = 0.0
+    return result.astype(np.float32, copy=False)
+
+
+def wavetable_indices(raw, mode, wt_extent):
+    """wavetable_pe.py:133-159 -> (indices, out-of-bounds mask or None)."""
+    wt_start, wt_end = wt_extent
+    finite = wt_start is not None and wt_end is not None
+    if mode == "wrap" and finite:
+        return ((raw - wt_start) % (wt_end - wt_start)) + wt_start, None
+    if mode == "clamp" and finite:
+        return np.clip(raw, wt_start, wt_end - 1), None
+    return raw, ((raw < wt_start) | (raw >= wt_end)) if finite else None
+
+
+def timewarp_step(pos, rate_values, src_extent):
+    """timewarp_pe.py:152-175 -> (indices, out-of-bounds mask or None, the head after the block)."""
+    duration = len(rate_values)
+    if duration == 1:
+        indices = np.array([pos], dtype=np.float64)
+    else:
+        prefix = np.concatenate(([0.0], np.cumsum(rate_values[:-1], dtype=np.float64)))
+        indices = pos + prefix
+    new_pos = float(pos + np.sum(rate_values, dtype=np.float64))
+    oob_mask = None
+    if src_extent[0] is not None or src_extent[1] is not None:
+        oob = np.zeros((duration,), dtype=bool)
+        if src_extent[0] is not None:
+            oob |= indices < float(src_extent[0])
+        if src_extent[1] is not None:
+            oob |= indices >= float(src_extent[1])
+        if np.any(oob):
+            oob_mask = oob
+    return indices, oob_mask, new_pos
+
+
+def timewarp_extent(src_extent, rate):
+    """timewarp_pe.py:101-135 (scalar rate)."""
+    if src_extent[0] is None or src_extent[1] is None:
+        return INF
+    src_start, src_end, r, p0 = float(src_extent[0]), float(src_extent[1]), float(rate), 0.0
+    if r == 0.0:
+        return INF if src_start <= p0 < src_end else (0, 0)
+    if r > 0.0:
+        n_start = int(np.ceil((src_start - p0) / r)) if src_start > p0 else 0
+        n_end = int(np.ceil((src_end - p0) / r))
+        n_start = max(0, n_start)
+        return (n_start, max(n_start, n_end))
+    n_start = max(0, int(np.floor((src_end - p0) / r)) + 1)
+    n_end = int(np.floor((src_start - p0) / r)) + 1
+    return (n_start, max(n_start, n_end))
+
+
+# ---------------------------------------------------------------------------------------------- graph evaluation
+class PlaybackNode(Node):
+    """oracle.graph_eval.Node plus the two new kinds, at any depth of the graph."""
+
+    def __init__(self, spec, sr, shared=None):
+        super().__init__(spec, sr, {})
+        for k, v in self.kw.items():
+            if is_spec(v):
+                self.sub[k] = PlaybackNode(v, sr)
+            elif k == "inputs":
+                self.sub[k] = [PlaybackNode(s, sr) for s in v]
+        self.positions = []          # TimeWarpPE: the float64 positions and rates of every block rendered so far
+        self.rates = []
+        self.reset()
+
+    def reset(self, recursive=True):
+        self.pos = 0.0
+        super().reset(recursive)
+
+    def channels(self):
+        if self.kind == "WavetablePE":
+            return self.sub["wavetable"].channels()
+        return super().channels()
+
+    def extent(self):
+        if self.kind == "WavetablePE":
+            return self.sub["indexer"].extent()
+        if self.kind == "TimeWarpPE":
+            if "rate" in self.sub:
+                return self.sub["rate"].extent()
+            return timewarp_extent(self.sub["source"].extent(), self.kw.get("rate", 1.0))
+        return super().extent()
+
+    def render(self, start, n):
+        if self.kind not in NEW_KINDS or n == 0:
+            return super().render(start, n)
+        cubic = self.kw.get("interpolation", "linear") == "cubic"
+        if self.kind == "WavetablePE":
+            raw = self.sub["indexer"].render(start, n)[:, 0].astype(np.float64)
+            table = self.sub["wavetable"]
+            indices, oob = wavetable_indices(raw, self.kw.get("out_of_bounds", "zero"), table.extent())
+            return interpolated_lookup(table.render, indices, cubic, oob)
+        if "rate" in self.sub:
+            rate_values = self.sub["rate"].render(start, n)[:, 0].astype(np.float64)
+        else:
+            rate_values = np.full((n,), float(self.kw.get("rate", 1.0)), dtype=np.float64)
+        source = self.sub["source"]
+        indices, oob, self.pos = timewarp_step(self.pos, rate_values, source.extent())
+        self.positions.append(indices)
+        self.rates.append(rate_values)
+        return interpolated_lookup(source.render, indices, cubic, oob)
+
+
+def find_nodes(node, kind):
+    out = [node] if node.kind == kind else []
+    for s in node.sub.values():
+        for c in (s if isinstance(s, list) else [s]):
+            out += find_nodes(c, kind)
+    return out
+
+
+def run_case(case):
+    """Every block of a case through the restatement; `ops` entries of the case ("reset" / "restart" before a block
+    index) are applied as the generator applies them to the reference graph."""
+    g = PlaybackNode(case["graph"], case["sr"])
+    ops = {int(k): v for k, v in case.get("ops", {}).items()}
+    outs = []
+    for i, (s, n) in enumerate(case["blocks"]):
+        if ops.get(i) == "restart":
+            g.reset()
+        elif ops.get(i) == "reset":
+            for node in find_nodes(g, "TimeWarpPE"):
+                node.reset(recursive=False)
+        outs.append(g.render(int(s), int(n)))
+    return outs, g
