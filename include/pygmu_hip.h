@@ -608,6 +608,39 @@ int pgx_gate_stateful(float *out, int64_t n, double sample_rate, double freq, do
                       const float *freq_stream, const float *duty_stream, const float *phase_stream,
                       double *state);
 
+/* ---- control-signal PEs (pgx_control.hip) ------------------------------------------------------------------
+ * SampleHoldPE._render (sample_hold_pe.py:73-85) / TrackHoldPE._render (track_hold_pe.py:73-85):
+ *   out[i] = src[j][0], j = the last frame <= i with control[j][0] > threshold (0.0 / 0.5, compared in float32);
+ *   (float)state[0] where this render has had none yet.  A max-scan over frame indices and a gather: bit-exact.
+ * Only channel 0 of src / control is read, in place (the *_channels are the strides).  state = { held value }: the
+ * float64 initial value until the first latch, a widened float32 sample afterwards.
+ * workspace: PGX_CONTROL_WORKSPACE_DOUBLES * 8 bytes of device scratch (the segments' last passing indices and a
+ * copy of the carried value). */
+#define PGX_CONTROL_WORKSPACE_DOUBLES 1040
+int pgx_hold(float *out, const float *src, int src_channels, const float *control, int control_channels, int64_t n,
+             float threshold, double *state, void *workspace);
+/* SlewLimiterPE._render (slew_limiter_pe.py:103-135), channel 0 of `in`.  mode 0 LINEAR (:116-124): up / down =
+ * rise_rate / sr, fall_rate / sr; mode 1 EXPONENTIAL (:125-132): up / down = min(rate / sr, 1).  Solved time-parallel
+ * (Newton rounds over affine pieces; from 131 072 frames on all 8192-frame windows together, with a sequential
+ * kernel armed if those rounds run out): samples within ~1e-13 relative of the sequential loop's float64 values.
+ * state = { current }; scratch: pgx_slew_scratch_bytes(n).  stats (NULL, or 4 device ints that are added to):
+ * inner Newton rounds, windows solved, window-level rounds, fallbacks to the sequential kernel. */
+size_t pgx_slew_scratch_bytes(int64_t n);
+int pgx_slew(float *out, const float *in, int in_channels, int64_t n, int mode, double up, double down,
+             double *state, double *scratch, int *stats);
+/* FunctionGenPE._render, every parameter a scalar (function_gen_pe.py:166-168, :180-193): phase =
+ * mod(mod((start + i) * dt, 1) + phase, 1); rectangle +-1 (:186) or _piecewise_linear (:121-155); `channels`
+ * copies of the column.  duty is clipped to [0, 1] here (:184).  Bit-exact. */
+int pgx_function_gen_pure(float *out, int64_t start, int64_t n, int channels, int sawtooth, double dt, double phase,
+                          double duty);
+/* FunctionGenPE._render with any PE parameter (function_gen_pe.py:169-177): base = mod(state[0] + [0,
+ * cumsum(f / sr)[:-1]], 1), then state[0] = mod(state[0] + sum(f / sr), 1); the float64 prefix sum runs over
+ * workgroup segments.  A stream pointer (mono, n floats) overrides its scalar; the host zeroes the state when a
+ * render does not continue the previous one (:170-171).  workspace: PGX_CONTROL_WORKSPACE_DOUBLES doubles. */
+int pgx_function_gen_stateful(float *out, int64_t n, int channels, int sawtooth, double sample_rate, double freq,
+                              double duty, double phase, const float *freq_stream, const float *duty_stream,
+                              const float *phase_stream, double *state, double *workspace);
+
 /* AdsrGatedPE._render (adsr_pe.py:124-196) / AdsrTriggeredPE._render (adsr_pe.py:279-335):
  * the reference's sequential float64 accumulation reproduced bit for bit (binade-linear runs, see
  * pgx_adsr.hip).  state[instance] = {state enum, env, prev_gate | sustain_ends_at}.

@@ -6,7 +6,8 @@ ProcessingElement / SourcePE / Snippet / Extent / Renderer / NullRenderer and th
 SinePE, BlitSawPE, SuperSawPE, BiquadPE, LadderPE, CombPE, MixPE, GainPE, ConvolvePE,
 AdsrGatedPE, AdsrTriggeredPE, PeriodicGate, PeriodicTrigger, ConstantPE, ArrayPE,
 DiracPE, IdentityPE, CachePE, CropPE, SVFilterPE, EnvelopePE, TransformPE, DelayPE, PiecewisePE,
-TriggerRestartPE, ReverbPE, WavWriterPE, WavReaderPE, KarplusStrongPE, AnalogOscPE, WavetablePE, TimeWarpPE
+TriggerRestartPE, ReverbPE, WavWriterPE, WavReaderPE, KarplusStrongPE, AnalogOscPE, WavetablePE, TimeWarpPE,
+SampleHoldPE, TrackHoldPE, SlewLimiterPE, FunctionGenPE
 (+ render_to_file, rho_for_decay_db).  Snippet payloads live in HBM; all DSP runs in
 hand-written HIP kernels for gfx950 behind the C ABI of include/pygmu_hip.h.
 """
@@ -62,6 +63,13 @@ from .analog_osc_pe import AnalogOscPE
 # arrive with the change that enters the two classes into that census.  tests/test_gpu_playback_fuzz.py stands in.
 from .wavetable_pe import OutOfBoundsMode, WavetablePE
 from .timewarp_pe import TimeWarpPE
+# The control-signal PEs: the same arrangement -- bound here (pg.SampleHoldPE, pg.TrackHoldPE, pg.SlewLimiterPE, pg.SlewMode,
+# pg.FunctionGenPE work) but NOT in __all__ until they have fuzz-corpus cases and evaluators under oracle/;
+# tests/test_gpu_control_fuzz.py stands in.
+from .sample_hold_pe import SampleHoldPE
+from .track_hold_pe import TrackHoldPE
+from .slew_limiter_pe import SlewLimiterPE, SlewMode
+from .function_gen_pe import FunctionGenPE
 from .utils import render_to_file
 from . import device, diagnostics
 

@@ -32,6 +32,7 @@ SOURCES = [
     "pgx_fftconv.hip",
     "pgx_comm.hip",
     "pgx_sources.hip",
+    "pgx_control.hip",
 ]
 
 # -ffp-contract=off: the parity contract is "same float64 operation order as the reference's

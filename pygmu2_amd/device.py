@@ -107,6 +107,11 @@ _SIGNATURES = [
     ("pgx_window", _I, [_P, _P, _L, _I, _L, _I, _I, _P]),
     ("pgx_dynamics", _I, [_P, _P, _P, _L, _I, _I, _P]),
     ("pgx_gate_stateful", _I, [_P, _L, _D, _D, _D, _D, _P, _P, _P, _P]),
+    ("pgx_hold", _I, [_P, _P, _I, _P, _I, _L, _F, _P, _P]),
+    ("pgx_slew_scratch_bytes", _Z, [_L]),
+    ("pgx_slew", _I, [_P, _P, _I, _L, _I, _D, _D, _P, _P, _P]),
+    ("pgx_function_gen_pure", _I, [_P, _L, _L, _I, _I, _D, _D, _D]),
+    ("pgx_function_gen_stateful", _I, [_P, _L, _I, _I, _D, _D, _D, _D, _P, _P, _P, _P, _P]),
     ("pgx_interp_lookup", _I, [_P, _P, _L, _L, _I, _L, _L, _D, _P, _I, _I, _D, _D]),
     ("pgx_index_range", _I, [_P, _P, _L, _L]),
     ("pgx_wavetable", _I, [_P, _P, _L, _P, _L, _L, _I, _I, _I, _I, _D, _D]),
