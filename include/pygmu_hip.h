@@ -796,6 +796,38 @@ int pgx_analog_osc_stateful(float *out, int64_t n, int channels, double sample_r
                             double duty, const float *freq_stream, const float *duty_stream, int restart,
                             double *state /* [2] */, void *workspace);
 
+/* ------------------------------------------------------------------ NoisePE (pgx_noise.hip)
+ * NoisePE._render (noise_pe.py:111-165): np.random.default_rng(seed).uniform(-1, 1, n).astype(float32) drawn on the
+ * device (numpy's PCG64: a 128-bit LCG with the XSL-RR output, reached at any draw number by a table skip-ahead), then
+ * white as drawn, Paul Kellet's pink filter, or the clamped brown walk, in the reference's float32 operation order:
+ * bit-exact, however a stream is cut into renders.  `batch` independent instances; instance i writes n frames at
+ * out + i * out_stride, reads params[i] and carries state[i] (pink and brown).  An instance's first frame is draw number
+ * params[i].consumed + draws of its stream (modulo 2^64); the caller adds n to `draws` after every render.  White is
+ * one launch of many workgroups; pink and brown are one launch of a workgroup per instance that steps the recurrence
+ * literally.
+ * pgx_noise_skip_table: the 64 pairs (M^(2^k), S_(2^k)) the skip-ahead uses, as {a_hi, a_lo, c_hi, c_lo} per k
+ * (256 words); needs no device. */
+typedef struct {
+    uint64_t state_hi, state_lo;   /* PCG64 state and increment as numpy reports them for the seed */
+    uint64_t inc_hi, inc_lo;
+    int64_t consumed;              /* draws taken from the stream before `draws` started counting */
+    int32_t scaled;                /* 0: (min_value, max_value) == (-1, 1), the draw passes untouched */
+    float span;                    /* float32(max_value - min_value) */
+    float min_value;               /* float32(min_value) */
+    int32_t pad;
+} pgx_noise_params;
+typedef struct {
+    float pink[7];                 /* b0..b6 */
+    float brown;                   /* the level */
+} pgx_noise_state;
+int pgx_noise_skip_table(uint64_t *table /* [256] */);
+int pgx_noise_white(float *out, int64_t out_stride, int batch, int64_t n, uint64_t draws,
+                    const pgx_noise_params *params);
+int pgx_noise_pink(float *out, int64_t out_stride, int batch, int64_t n, uint64_t draws,
+                   const pgx_noise_params *params, pgx_noise_state *state);
+int pgx_noise_brown(float *out, int64_t out_stride, int batch, int64_t n, uint64_t draws,
+                    const pgx_noise_params *params, pgx_noise_state *state);
+
 #ifdef __cplusplus
 }
 #endif

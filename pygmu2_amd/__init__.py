@@ -7,7 +7,7 @@ SinePE, BlitSawPE, SuperSawPE, BiquadPE, LadderPE, CombPE, MixPE, GainPE, Convol
 AdsrGatedPE, AdsrTriggeredPE, PeriodicGate, PeriodicTrigger, ConstantPE, ArrayPE,
 DiracPE, IdentityPE, CachePE, CropPE, SVFilterPE, EnvelopePE, TransformPE, DelayPE, PiecewisePE,
 TriggerRestartPE, ReverbPE, WavWriterPE, WavReaderPE, KarplusStrongPE, AnalogOscPE, WavetablePE, TimeWarpPE,
-SampleHoldPE, TrackHoldPE, SlewLimiterPE, FunctionGenPE
+SampleHoldPE, TrackHoldPE, SlewLimiterPE, FunctionGenPE, NoisePE
 (+ render_to_file, rho_for_decay_db).  Snippet payloads live in HBM; all DSP runs in
 hand-written HIP kernels for gfx950 behind the C ABI of include/pygmu_hip.h.
 """
@@ -70,6 +70,9 @@ from .sample_hold_pe import SampleHoldPE
 from .track_hold_pe import TrackHoldPE
 from .slew_limiter_pe import SlewLimiterPE, SlewMode
 from .function_gen_pe import FunctionGenPE
+# NoisePE / NoiseMode: again the same arrangement (pg.NoisePE, pg.NoiseMode work, neither is in __all__);
+# tests/test_gpu_noise_fuzz.py stands in for the census.
+from .noise_pe import NoiseMode, NoisePE
 from .utils import render_to_file
 from . import device, diagnostics
 

@@ -33,6 +33,7 @@ SOURCES = [
     "pgx_comm.hip",
     "pgx_sources.hip",
     "pgx_control.hip",
+    "pgx_noise.hip",
 ]
 
 # -ffp-contract=off: the parity contract is "same float64 operation order as the reference's

@@ -34,6 +34,7 @@ _L = C.c_int64
 _D = C.c_double
 _F = C.c_float
 _Z = C.c_size_t
+_U = C.c_uint64
 
 _SIGNATURES = [
     ("pgx_abi_version", _I, []),
@@ -177,6 +178,10 @@ _SIGNATURES = [
     ("pgx_analog_osc_workspace_bytes", _Z, [_L]),
     ("pgx_analog_osc_pure", _I, [_P, _L, _L, _I, _D, _I, _D, _D, _P]),
     ("pgx_analog_osc_stateful", _I, [_P, _L, _I, _D, _I, _D, _D, _P, _P, _I, _P, _P]),
+    ("pgx_noise_skip_table", _I, [_P]),
+    ("pgx_noise_white", _I, [_P, _L, _I, _L, _U, _P]),
+    ("pgx_noise_pink", _I, [_P, _L, _I, _L, _U, _P, _P]),
+    ("pgx_noise_brown", _I, [_P, _L, _I, _L, _U, _P, _P]),
 ]
 
 EXPORTED_SYMBOLS = [s[0] for s in _SIGNATURES]
@@ -200,6 +205,9 @@ GATE_PARAMS = np.dtype([("dt", "<f8"), ("phase", "<f8"), ("duty", "<f8")])
 KS_PARAMS = np.dtype([("line_offset", "<i8"), ("n", "<i4"), ("two_phase", "<i4"), ("switch_at", "<i8"),
                       ("rho", "<f4"), ("rho_damping", "<f4"), ("c", "<f4"), ("pad", "<f4")])
 KS_STATE = np.dtype([("r", "<i4"), ("ap_in", "<f4"), ("ap_out", "<f4"), ("pad", "<i4")])
+NOISE_PARAMS = np.dtype([("state_hi", "<u8"), ("state_lo", "<u8"), ("inc_hi", "<u8"), ("inc_lo", "<u8"),
+                         ("consumed", "<i8"), ("scaled", "<i4"), ("span", "<f4"), ("min_value", "<f4"), ("pad", "<i4")])
+NOISE_STATE = np.dtype([("pink", "<f4", (7,)), ("brown", "<f4")])
 ADSR_PARAMS = np.dtype([("attack_dvdt", "<f8"), ("decay_dvdt", "<f8"), ("release_dvdt", "<f8"),
                         ("sustain_level", "<f8"), ("sustain_samples", "<i8")])
 
