@@ -828,6 +828,35 @@ int pgx_noise_pink(float *out, int64_t out_stride, int batch, int64_t n, uint64_
 int pgx_noise_brown(float *out, int64_t out_stride, int batch, int64_t n, uint64_t draws,
                     const pgx_noise_params *params, pgx_noise_state *state);
 
+/* ------------------------------------------------------------------ arbitrary-length DFT, TralfamPE (pgx_spectral.hip)
+ * Complex float64 DFT of any length 1 <= n <= pgx_dft_max_length() = 2^21, `batch` sequences of n {double re, im}
+ * points lying n apart; numpy's convention: forward unnormalised, inverse scaled 1/n.  A power of two is a Stockham
+ * FFT held in LDS (n <= 2048: one launch) or the four-step decomposition (two launches); every other length is
+ * Bluestein's chirp-z over M = 2^ceil(log2(2n - 1)) points with the chirp phase k^2 mod 2n reduced in 64-bit
+ * integers.  Every twiddle is evaluated in float64 from an exactly reduced index, never recurred.
+ *   pgx_dft_plan_bytes / pgx_dft_plan   what depends on n alone (the chirp and its spectrum; for a power of two the
+ *                                       plan is empty but must still be a valid 16-byte block), made once per length
+ *   pgx_dft_workspace_bytes             scratch of one call; 0 for an unsupported n or batch
+ *   pgx_dft_c2c                         out == in is allowed; out, in, plan and workspace are device memory
+ * The three *_bytes helpers and pgx_dft_max_length are pure planning helpers: they need no device.  A longer n is
+ * PGX_ERR_INVALID.
+ *
+ * pgx_tralfam: TralfamPE._mogrify (tralfam_pe.py:88-105) for x = float32 (n, channels) interleaved: per channel the
+ * DFT of the whole extent, magnitudes kept, every phase replaced by rng.random((n, channels)) * 2.0 * pi -- draw
+ * k * channels + c of the PCG64 stream that rng[0] describes (state, inc, consumed; the other fields are not read), as
+ * u = (raw >> 11) * 2^-53 -- inverse DFT, real part rounded to float32 into out (n, channels).  normalize_peak > 0:
+ * then the max |out| over all channels is reduced on the device and out is scaled in place by
+ * float32(normalize_peak) / peak (float32 division and product; nothing when the peak is 0).  plan: pgx_dft_plan of n;
+ * workspace: pgx_tralfam_workspace_bytes(n, channels). */
+int64_t pgx_dft_max_length(void);
+size_t pgx_dft_plan_bytes(int64_t n);
+size_t pgx_dft_workspace_bytes(int64_t n, int batch);
+int pgx_dft_plan(void *plan, int64_t n);
+int pgx_dft_c2c(void *out, const void *in, int64_t n, int batch, int inverse, const void *plan, void *workspace);
+size_t pgx_tralfam_workspace_bytes(int64_t n, int channels);
+int pgx_tralfam(float *out, const float *x, int64_t n, int channels, const pgx_noise_params *rng,
+                double normalize_peak /* <= 0: none */, const void *plan, void *workspace);
+
 #ifdef __cplusplus
 }
 #endif

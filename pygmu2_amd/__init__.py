@@ -7,7 +7,7 @@ SinePE, BlitSawPE, SuperSawPE, BiquadPE, LadderPE, CombPE, MixPE, GainPE, Convol
 AdsrGatedPE, AdsrTriggeredPE, PeriodicGate, PeriodicTrigger, ConstantPE, ArrayPE,
 DiracPE, IdentityPE, CachePE, CropPE, SVFilterPE, EnvelopePE, TransformPE, DelayPE, PiecewisePE,
 TriggerRestartPE, ReverbPE, WavWriterPE, WavReaderPE, KarplusStrongPE, AnalogOscPE, WavetablePE, TimeWarpPE,
-SampleHoldPE, TrackHoldPE, SlewLimiterPE, FunctionGenPE, NoisePE
+SampleHoldPE, TrackHoldPE, SlewLimiterPE, FunctionGenPE, NoisePE, TralfamPE, SlicePE, SetExtentPE
 (+ render_to_file, rho_for_decay_db).  Snippet payloads live in HBM; all DSP runs in
 hand-written HIP kernels for gfx950 behind the C ABI of include/pygmu_hip.h.
 """
@@ -73,6 +73,13 @@ from .function_gen_pe import FunctionGenPE
 # NoisePE / NoiseMode: again the same arrangement (pg.NoisePE, pg.NoiseMode work, neither is in __all__);
 # tests/test_gpu_noise_fuzz.py stands in for the census.
 from .noise_pe import NoiseMode, NoisePE
+# TralfamPE, SlicePE, SetExtentPE and the `spectral` module (the arbitrary-length DFT behind TralfamPE): the same
+# arrangement once more (pg.TralfamPE, pg.SlicePE, pg.SetExtentPE work, none is in __all__); tests/test_gpu_tralfam.py
+# renders them against fixtures of the reference.
+from .set_extent_pe import SetExtentPE
+from .slice_pe import SlicePE
+from .tralfam_pe import TralfamPE
+from . import spectral
 from .utils import render_to_file
 from . import device, diagnostics
 

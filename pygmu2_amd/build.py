@@ -34,6 +34,7 @@ SOURCES = [
     "pgx_sources.hip",
     "pgx_control.hip",
     "pgx_noise.hip",
+    "pgx_spectral.hip",
 ]
 
 # -ffp-contract=off: the parity contract is "same float64 operation order as the reference's
@@ -53,7 +54,8 @@ def _hipcc() -> str:
 
 
 def _deps_common():
-    return [os.path.join(CSRC, "pgx_common.h"), os.path.join(ROOT, "include", "pygmu_hip.h"),
+    return [os.path.join(CSRC, "pgx_common.h"), os.path.join(CSRC, "pgx_pcg.h"),
+            os.path.join(ROOT, "include", "pygmu_hip.h"),
             os.path.abspath(__file__)]
 
 

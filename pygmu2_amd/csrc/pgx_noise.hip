@@ -21,33 +21,18 @@
 // -ffp-contract=off each `*` and `+` below is one rounding, in the reference's order.  Constants are the float64
 // literals of the reference rounded to float32, as numpy rounds a Python float that meets a float32.
 
-#include "pgx_common.h"
+#include "pgx_pcg.h"
 
 namespace {
 
-typedef unsigned __int128 u128;
+using pgx::kPcgMult;
+using pgx::make128;
+using pgx::SkipTable;
+using pgx::u128;
 
-constexpr u128 kPcgMult = ((u128)0x2360ED051FC65DA4ULL << 64) | (u128)0x4385DF649FCCF645ULL;
-
-struct SkipTable {
-    u128 a[64];     // M^(2^k)
-    u128 c[64];     // S_(2^k) = 1 + M + ... + M^(2^k - 1)
-};
-
-constexpr SkipTable make_skip_table() {
-    SkipTable t{};
-    u128 a = kPcgMult, c = 1;
-    for (int k = 0; k < 64; ++k) {
-        t.a[k] = a;
-        t.c[k] = c;
-        c = c * (a + 1);        // S_2n = S_n + M^n * S_n
-        a = a * a;
-    }
-    return t;
-}
-
-constexpr SkipTable kSkipHost = make_skip_table();
-__constant__ SkipTable kSkip = make_skip_table();
+// the library's one skip table (pgx_pcg.h); other translation units read it through pgx::pcg_skip_table_device()
+constexpr SkipTable kSkipHost = pgx::make_skip_table();
+__constant__ SkipTable kSkip = pgx::make_skip_table();
 
 constexpr int kLanes = 256;
 constexpr int kWhiteRun = 8;                          // consecutive samples per lane and tile
@@ -60,22 +45,12 @@ constexpr int kSeqTile = 1 << kSeqTileLog2;           // kLanes * kSeqRun
 constexpr int kSeqGroup = 8;                          // samples of a stepped chain held in registers at a time
 static_assert(kWhiteTile == kLanes * kWhiteRun && kSeqTile == kLanes * kSeqRun, "tile geometry");
 
-__device__ __forceinline__ u128 make128(uint64_t hi, uint64_t lo) { return ((u128)hi << 64) | (u128)lo; }
-
 // `d` LCG steps from s
-__device__ __forceinline__ u128 pcg_skip(u128 s, u128 inc, uint64_t d) {
-    for (int k = 0; d != 0; ++k, d >>= 1)
-        if (d & 1) s = kSkip.a[k] * s + kSkip.c[k] * inc;
-    return s;
-}
+__device__ __forceinline__ u128 pcg_skip(u128 s, u128 inc, uint64_t d) { return pgx::pcg_skip_with(kSkip, s, inc, d); }
 
 // the draw that numpy takes from state s (already stepped): float32(-1.0 + 2.0 * ((xsl_rr(s) >> 11) * 2^-53))
 __device__ __forceinline__ float pcg_draw(u128 s) {
-    const uint64_t hi = (uint64_t)(s >> 64), lo = (uint64_t)s;
-    const uint64_t x = hi ^ lo;
-    const unsigned rot = (unsigned)(hi >> 58);
-    const uint64_t u = (x >> rot) | (x << ((64u - rot) & 63u));
-    const double r = (double)(u >> 11) * 0x1p-53;
+    const double r = (double)(pgx::pcg_output(s) >> 11) * 0x1p-53;
     return (float)(-1.0 + 2.0 * r);
 }
 
@@ -298,6 +273,20 @@ __global__ __launch_bounds__(kLanes) void k_noise_brown(float *out, int64_t out_
 }
 
 }  // namespace
+
+namespace pgx {
+
+const SkipTable *pcg_skip_table_device() {
+    void *p = nullptr;
+    const hipError_t e = hipGetSymbolAddress(&p, HIP_SYMBOL(kSkip));
+    if (e != hipSuccess) {
+        fail(PGX_ERR_RUNTIME, std::string("pcg_skip_table_device: ") + hipGetErrorString(e));
+        return nullptr;
+    }
+    return static_cast<const SkipTable *>(p);
+}
+
+}  // namespace pgx
 
 extern "C" {
 

@@ -182,6 +182,13 @@ _SIGNATURES = [
     ("pgx_noise_white", _I, [_P, _L, _I, _L, _U, _P]),
     ("pgx_noise_pink", _I, [_P, _L, _I, _L, _U, _P, _P]),
     ("pgx_noise_brown", _I, [_P, _L, _I, _L, _U, _P, _P]),
+    ("pgx_dft_max_length", _L, []),
+    ("pgx_dft_plan_bytes", _Z, [_L]),
+    ("pgx_dft_workspace_bytes", _Z, [_L, _I]),
+    ("pgx_dft_plan", _I, [_P, _L]),
+    ("pgx_dft_c2c", _I, [_P, _P, _L, _I, _I, _P, _P]),
+    ("pgx_tralfam_workspace_bytes", _Z, [_L, _I]),
+    ("pgx_tralfam", _I, [_P, _P, _L, _I, _P, _D, _P, _P]),
 ]
 
 EXPORTED_SYMBOLS = [s[0] for s in _SIGNATURES]

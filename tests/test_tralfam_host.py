@@ -1,0 +1,192 @@
+"""CPU: TralfamPE, SlicePE, SetExtentPE and the arbitrary-length DFT without a device.  The float64 restatement
+(tests/tralfam_oracle.py) reproduces every stored sample of the reference-rendered fixtures within the bound the cases
+are held to; the model of the device's draws equals default_rng(seed).random bit for bit, row-major for two channels,
+at near and far offsets; the Bluestein model with the integer chirp reduction equals np.fft.fft within the DFT bound;
+the classes' host side -- validation, repr, extent, purity, channel count, inputs, export -- is the reference's as the
+fixtures recorded it; the planning helpers of the C ABI answer without a device."""
+
+import numpy as np
+import pytest
+
+import pygmu2_amd as pg
+import tralfam_oracle as T
+from pygmu2_amd import device
+from pygmu2_amd.build import build
+
+CASES, NPZ = T.load_cases()
+ALL = CASES["cases"]
+BY_NAME = {c["name"]: c for c in ALL}
+OFFSETS = (0, 1, 2 ** 20 + 3, 2 ** 32 + 1, 2 ** 40)
+LENGTHS = (1, 2, 3, 7, 128, 1000, 4096, 65_536, 4097, 16_964, 105_164, 99_991, 132_300, 156_168, 1_048_577,
+           2 ** 21 - 1, 2 ** 21)
+
+
+def pg_namespace():
+    import types
+    K = types.SimpleNamespace(ArrayPE=pg.ArrayPE, DelayPE=pg.DelayPE, LoopPE=pg.LoopPE, CropPE=pg.CropPE,
+                              NoisePE=pg.NoisePE, TralfamPE=pg.TralfamPE, SlicePE=pg.SlicePE,
+                              SetExtentPE=pg.SetExtentPE, ExtendMode=pg.ExtendMode)
+    K.wav = lambda name: pg.WavReaderPE(T.wav_path(name))
+    return K
+
+
+@pytest.fixture(scope="module")
+def lib():
+    build()
+    return device.load_library()
+
+
+def test_fixture_census():
+    assert int(CASES["numpy"].split(".")[0]) >= 2
+    plain = {c["source"].get("n") for c in ALL if c["graph"] == "plain" and c["source"]["kind"] != "array"}
+    for n in (1, 2, 3, 7, 128, 1000, 4096, 65_536, 4097, 16_964, 105_164, 99_991, 132_300, 156_168, 1_048_577,
+              2 ** 21 - 1, 2 ** 21):
+        assert n in plain, n
+    seeds = {c.get("seed") for c in ALL if c["compare"] == "peak"}
+    assert set(T.SEEDS) <= seeds and None in seeds
+    assert {c["graph"] for c in ALL} == {"plain", "delay", "loop", "example", "noise_crop", "slice", "set_extent"}
+    assert {c["extend_mode"] for c in ALL if c["graph"] == "set_extent"} == {"zero", "hold_first", "hold_last", "hold_both"}
+
+
+@pytest.mark.parametrize("case", ALL, ids=[c["name"] for c in ALL])
+def test_restatement_equals_fixture(case):
+    outs = T.restate_case(case, NPZ)
+    got, want = T.stored_of(case, outs), NPZ[case["name"]]
+    assert got.shape == want.shape
+    if case["compare"] == "bits":
+        assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), case["name"]
+        return
+    err = float(np.max(np.abs(got.astype(np.float64) - want.astype(np.float64)))) if want.size else 0.0
+    if case["compare"] == "peak":
+        peak = case["peak"]
+        if case["store"] == "sampled":
+            assert float(np.max(np.abs(want))) == peak              # the peak is among the stored frames
+            assert float(np.max(np.abs(outs[0]))) == pytest.approx(peak, rel=1e-6)
+        if peak == 0.0:
+            assert not np.any(got), f"{case['name']}: a silent case must be exactly zero"
+        bound = T.PEAK_BOUND * peak
+    else:
+        bound = T.REL_TOL * float(np.max(np.abs(want))) + T.ABS_FLOOR
+    assert err <= bound, f"{case['name']}: {err:.3g} > {bound:.3g}"
+
+
+@pytest.mark.parametrize("seed", T.SEEDS)
+def test_model_draws_equal_numpy_random(seed):
+    for offset in OFFSETS:
+        want = T.numpy_random(seed, offset, 64)
+        got = T.model_random(seed, offset, 64)
+        assert np.array_equal(got.view(np.uint64), want.view(np.uint64)), (seed, offset)
+    # rng.random((n, 2)) fills row-major: element (k, c) is draw 2k + c
+    two = np.random.default_rng(seed).random((50, 2))
+    flat = T.model_random(seed, 0, 100)
+    assert np.array_equal(two.view(np.uint64), flat.reshape(50, 2).view(np.uint64))
+    # the conversion the kernel restates: (raw >> 11) * 2^-53
+    raw = np.random.PCG64(seed).random_raw(16)
+    assert np.array_equal((raw >> np.uint64(11)).astype(np.float64) * 2.0 ** -53, np.random.default_rng(seed).random(16))
+
+
+@pytest.mark.parametrize("n", LENGTHS)
+def test_bluestein_model_within_the_dft_bound(n):
+    rng = np.random.default_rng(n)
+    x = rng.standard_normal(n) + 1j * rng.standard_normal(n)
+    ref = np.fft.fft(x)
+    err = float(np.max(np.abs(T.bluestein_dft(x) - ref)))
+    assert err <= T.dft_bound(n, ref), f"forward n={n}: {err:.3e} > {T.dft_bound(n, ref):.3e}"
+    ref = np.fft.ifft(x)
+    err = float(np.max(np.abs(T.bluestein_dft(x, inverse=True) - ref)))
+    assert err <= T.dft_bound(n, ref), f"inverse n={n}: {err:.3e} > {T.dft_bound(n, ref):.3e}"
+
+
+def test_chirp_phase_is_reduced_in_integers():
+    n = 2 ** 21 - 1
+    k = np.array([n - 1, n - 2, 1_500_000], dtype=np.int64)
+    exact = [int(v) ** 2 % (2 * n) for v in k]
+    assert list((k * k) % (2 * n)) == exact
+    got = T.chirp(n)[k]
+    want = np.exp(1j * np.pi * (np.array(exact, dtype=np.float64) / n))
+    assert np.array_equal(got, want)
+    # the float route the issue warns against is off by orders of magnitude more than an ulp
+    naive = np.exp(1j * np.pi * (k.astype(np.float64) ** 2) / n)
+    assert np.max(np.abs(naive - want)) > 1e-12
+
+
+@pytest.mark.parametrize("case", ALL, ids=[c["name"] for c in ALL])
+def test_host_side_equals_reference(case):
+    pg.set_sample_rate(case["sr"])
+    _, pe, _ = T.build_case(case, pg_namespace(), NPZ)
+    rec = case["pe"]
+    want_repr = rec["repr"].replace("ArrayPE", "WavReaderPE") if case["source"]["kind"] == "wav" and \
+        case["graph"] in ("plain", "slice", "set_extent") else rec["repr"]
+    assert repr(pe) == want_repr
+    ext = pe.extent()
+    assert [ext.start, ext.end] == rec["extent"]
+    assert pe.is_pure() == rec["pure"]
+    assert pe.channel_count() == rec["channels"]
+    assert [type(i).__name__ for i in pe.inputs()] == \
+        [("WavReaderPE" if name == "ArrayPE" and case["source"]["kind"] == "wav" else name) for name in rec["inputs"]]
+
+
+def test_validation_messages_and_export():
+    src = pg.ArrayPE(np.zeros(8, dtype=np.float32))
+    for bad in (0, -1.0, float("inf"), float("nan")):
+        with pytest.raises(ValueError, match="normalize_peak must be a positive finite number, got"):
+            pg.TralfamPE(src, normalize_peak=bad)
+    with pytest.raises(ValueError, match="duration must be >= 0, got -1"):
+        pg.SlicePE(src, 0, -1)
+    with pytest.raises(ValueError, match="duration must be >= 0, got -3"):
+        pg.SetExtentPE(src, 0, -3)
+    t = pg.TralfamPE(src, seed=3, normalize_peak=0.5)
+    assert repr(t) == "TralfamPE(source=ArrayPE, seed=3, normalize_peak=0.5)"
+    assert repr(pg.TralfamPE(src)) == "TralfamPE(source=ArrayPE)"
+    assert t.inputs() == [src] and t.is_pure() and t.channel_count() == 1
+    s = pg.SlicePE(src, 2, 4, fade_in_seconds=0.5)
+    assert (s.start, s.duration, s.fade_in_samples, s.fade_out_samples) == (2, 4, 22050, 0)
+    e = pg.SetExtentPE(src, None, 5)
+    assert (e.start, e.duration, e.end) == (None, 5, 5)
+    for name in ("TralfamPE", "SlicePE", "SetExtentPE", "spectral"):
+        assert hasattr(pg, name) and name not in pg.__all__
+    # windows: slices of the cached buffer depend on the frame index alone; over a stateful source no window at all
+    from pygmu2_amd import look_ahead, read_ahead
+    assert pg.TralfamPE._READ_AHEAD_SAFE and read_ahead.eligible(pg.GainPE(t, 0.5))
+    noisy = pg.TralfamPE(pg.CropPE(pg.NoisePE(seed=1), 0, 64))
+    assert not read_ahead.eligible(noisy) and not look_ahead.capable(pg.BiquadPE(noisy, frequency=500.0, q=1.0))
+
+
+def test_open_and_empty_extents_need_no_device():
+    pg.set_sample_rate(48000)
+    open_src = pg.SetExtentPE(pg.ArrayPE(np.ones(8, dtype=np.float32)), None, 5)
+    out = pg.TralfamPE(open_src, seed=1).render(-3, 10)
+    assert out.data.shape == (10, 1) and not np.any(out.data)          # an open side: zeros, no error
+    empty = pg.CropPE(pg.ArrayPE(np.ones(8, dtype=np.float32)), 3, 0)
+    with pytest.raises(ValueError, match="TralfamPE requires positive extent duration; got duration=0"):
+        pg.TralfamPE(empty).render(0, 4)
+    too_long = pg.SetExtentPE(pg.ArrayPE(np.ones(8, dtype=np.float32)), 0, 2 ** 21 + 1)
+    with pytest.raises(ValueError, match="2097152"):
+        pg.TralfamPE(too_long).render(0, 4)
+
+
+def test_planning_helpers_answer_without_a_device(lib):
+    limit = lib.pgx_dft_max_length()
+    assert limit == 2 ** 21
+    for n in (1, 2, 3, 2048, 4096, 16_964, limit - 1, limit):
+        assert lib.pgx_dft_workspace_bytes(n, 1) > 0
+        assert lib.pgx_dft_workspace_bytes(n, 3) >= lib.pgx_dft_workspace_bytes(n, 1)
+        assert lib.pgx_tralfam_workspace_bytes(n, 2) > lib.pgx_dft_workspace_bytes(n, 2)
+        assert lib.pgx_dft_plan_bytes(n) > 0
+    # Bluestein keeps batch padded sequences of M = 2^ceil(log2(2n-1)) points, the four-step pass as many again
+    m = T.fft_points(16_964)
+    assert lib.pgx_dft_workspace_bytes(16_964, 2) >= 2 * 2 * m * 16
+    assert lib.pgx_dft_plan_bytes(16_964) >= (16_964 + m) * 16
+    for n in (0, -5, limit + 1, 2 ** 40):
+        assert lib.pgx_dft_workspace_bytes(n, 1) == 0
+        assert lib.pgx_tralfam_workspace_bytes(n, 1) == 0
+        assert lib.pgx_dft_plan_bytes(n) == 0
+    assert lib.pgx_dft_workspace_bytes(1000, 0) == 0 and lib.pgx_tralfam_workspace_bytes(1000, 0) == 0
+
+
+@pytest.mark.skipif(device.device_available(), reason="a GPU is present")
+def test_entry_points_refuse_before_init(lib):
+    assert lib.pgx_dft_plan(None, 8) == -3
+    assert lib.pgx_dft_c2c(None, None, 8, 1, 0, None, None) == -3
+    assert lib.pgx_tralfam(None, None, 8, 1, None, 0.0, None, None) == -3
+    assert b"pgx_init" in lib.pgx_last_error()
