@@ -781,6 +781,27 @@ typedef struct {
 } pgx_ks_state;
 int pgx_karplus_strong(float *out, int64_t out_stride, int batch, int64_t start, int64_t n, int channels,
                        const pgx_ks_params *params, float *lines, pgx_ks_state *state, int max_line);
+/* The plucks of a score in one launch (MixPE over DelayPE / CropPE of KarplusStrongPE, sequence_pe.py / mix_pe.py:69-96):
+ * `count` strings, each with its own parameter block, line (line + params->line_offset), state, first frame in its own
+ * time (>= 0), frame count (>= 0) and destination out + dst (floats; frames * channels of them, disjoint from every
+ * other string's).  The same arithmetic as pgx_karplus_strong, string by string: bit-exact.  notes[] is device memory.
+ * `group` strings (1..64) share a workgroup; a workgroup whose lines fit in 64 KiB stages them in LDS, any other reads
+ * its lines in global memory.  max_line >= every params->n >= 2 (a workgroup holding a line outside that renders
+ * nothing).  Lanes of one workgroup
+ * run until the longest of them is done: the caller orders notes[] by frame count.  notes_on_host != 0: notes[] is
+ * HOST memory with count <= PGX_SCORE_INLINE entries, which travel in the kernel arguments (nothing is uploaded; the
+ * array may be reused as soon as the call returns). */
+typedef struct {
+    const pgx_ks_params *params;
+    float *line;
+    pgx_ks_state *state;
+    int64_t start;
+    int64_t frames;
+    int64_t dst;
+} pgx_ks_note;
+#define PGX_SCORE_INLINE 16
+int pgx_karplus_score(float *out, int channels, const pgx_ks_note *notes, int count, int group, int max_line,
+                      int notes_on_host);
 
 /* AnalogOscPE._render (analog_osc_pe.py:203-267), float64 inside, float32 out, `channels` identical copies.
  * waveform 0 = "rectangle", 1 = "sawtooth".  Pure form (scalar parameters): phase = mod(index * f / sr, 1)
@@ -856,6 +877,24 @@ int pgx_dft_c2c(void *out, const void *in, int64_t n, int batch, int inverse, co
 size_t pgx_tralfam_workspace_bytes(int64_t n, int channels);
 int pgx_tralfam(float *out, const float *x, int64_t n, int channels, const pgx_noise_params *rng,
                 double normalize_peak /* <= 0: none */, const void *plan, void *workspace);
+
+/* ------------------------------------------------------------------ score mix (pgx_score.hip)
+ * MixPE._render (mix_pe.py:69-96) over inputs that each occupy part of the block: out[f] = the float32 sum, in list
+ * order, one rounding per add, of the segments that cover frame f; 0 where none does.  A segment is `frames` frames of
+ * `channels` interleaved floats at `data`, the first of them frame `first` of the block (0 <= first,
+ * first + frames <= the block's frames).  The block is cut into tiles of tile_frames frames; tile t adds the segments
+ * tile_list[tile_offsets[t] .. tile_offsets[t + 1]) (indices into segs[], in the order they are to be added; the
+ * caller lists every segment that touches the tile, a listed segment that does not is harmless).  One workgroup per
+ * tile.  segs, tile_offsets (tiles + 1 entries) and tile_list are device memory; n_segs == 0 zero-fills.
+ * tile_list == NULL: segs is HOST memory with n_segs <= PGX_SCORE_INLINE entries, which travel in the kernel arguments
+ * (nothing is uploaded), and every tile walks all of them in order; tile_offsets is not read. */
+typedef struct {
+    const float *data;
+    int64_t first;
+    int64_t frames;
+} pgx_score_seg;
+int pgx_score_mix(float *out, int64_t frames, int channels, const pgx_score_seg *segs, int64_t n_segs,
+                  const int32_t *tile_offsets, const int32_t *tile_list, int64_t tile_frames);
 
 #ifdef __cplusplus
 }

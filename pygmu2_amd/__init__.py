@@ -7,8 +7,8 @@ SinePE, BlitSawPE, SuperSawPE, BiquadPE, LadderPE, CombPE, MixPE, GainPE, Convol
 AdsrGatedPE, AdsrTriggeredPE, PeriodicGate, PeriodicTrigger, ConstantPE, ArrayPE,
 DiracPE, IdentityPE, CachePE, CropPE, SVFilterPE, EnvelopePE, TransformPE, DelayPE, PiecewisePE,
 TriggerRestartPE, ReverbPE, WavWriterPE, WavReaderPE, KarplusStrongPE, AnalogOscPE, WavetablePE, TimeWarpPE,
-SampleHoldPE, TrackHoldPE, SlewLimiterPE, FunctionGenPE, NoisePE, TralfamPE, SlicePE, SetExtentPE
-(+ render_to_file, rho_for_decay_db).  Snippet payloads live in HBM; all DSP runs in
+SampleHoldPE, TrackHoldPE, SlewLimiterPE, FunctionGenPE, NoisePE, TralfamPE, SlicePE, SetExtentPE, SequencePE
+(+ render_to_file, rho_for_decay_db, pitch_to_freq and the other unit conversions).  Snippet payloads live in HBM; all DSP runs in
 hand-written HIP kernels for gfx950 behind the C ABI of include/pygmu_hip.h.
 """
 
@@ -80,6 +80,13 @@ from .set_extent_pe import SetExtentPE
 from .slice_pe import SlicePE
 from .tralfam_pe import TralfamPE
 from . import spectral
+# SequencePE / SequenceMode and the unit conversions: the same arrangement (pg.SequencePE, pg.SequenceMode,
+# pg.pitch_to_freq ... work, none is in __all__); tests/test_gpu_score.py renders scores against fixtures of the
+# reference.  score_bank is what MixPE renders such scores through.
+from .sequence_pe import SequenceMode, SequencePE
+from .conversions import (freq_to_pitch, pitch_to_freq, ratio_to_semitones, samples_to_seconds, seconds_to_samples,
+                          semitones_to_ratio)
+from . import score_bank
 from .utils import render_to_file
 from . import device, diagnostics
 

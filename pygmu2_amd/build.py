@@ -35,6 +35,7 @@ SOURCES = [
     "pgx_control.hip",
     "pgx_noise.hip",
     "pgx_spectral.hip",
+    "pgx_score.hip",
 ]
 
 # -ffp-contract=off: the parity contract is "same float64 operation order as the reference's

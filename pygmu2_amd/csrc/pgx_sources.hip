@@ -142,6 +142,72 @@ k_karplus_strong(float *out, int64_t out_stride, int batch, int64_t start, int64
     }
 }
 
+// The plucks of a score: string k of the launch is notes[k], with its own parameter block, line, state, first frame,
+// frame count and destination.  `group` strings per workgroup, a lane each (lanes group .. 63 only help to stage).  A
+// workgroup stages its lines in LDS at a stride of ITS longest line when they fit in the lds_floats the launch was
+// given, and otherwise works in global memory: one 1 Hz string does not take the other workgroups off the LDS path.
+// A launch of at most kKsInline strings carries notes[] in its kernel arguments (k_karplus_score_inline): nothing is
+// uploaded for it, which is what a streamed block of a score with a handful of sounding plucks needs.
+constexpr int kKsInline = PGX_SCORE_INLINE;
+struct KsInline {
+    pgx_ks_note n[kKsInline];
+};
+
+__device__ __forceinline__ void ks_score_body(float *ks_lds, float *out, int channels, const pgx_ks_note *notes,
+                                              int count, int group, int max_line, int lds_floats) {
+    const int first = blockIdx.x * group;
+    const int here = (count - first < group) ? count - first : group;
+    int stride = 2;
+    bool ok = true;
+    for (int k = 0; k < here; ++k) {
+        const int n = notes[first + k].params->n;
+        stride = n > stride ? n : stride;
+        ok = ok && n >= 2;                                 // (ks_run's chunks are N - 1 frames: N < 2 would never end)
+    }
+    ok = ok && stride <= max_line;                         // a line longer than the caller said: nothing is touched
+    const bool use_lds = ok && (int64_t)here * stride <= lds_floats;
+    if (use_lds) {
+        for (int k = 0; k < here; ++k) {
+            const pgx_ks_note q = notes[first + k];
+            const float *src = q.line + q.params->line_offset;
+            const int n = q.params->n;
+            for (int x = threadIdx.x; x < n; x += kKsLanes) ks_lds[k * stride + x] = src[x];
+        }
+        __syncthreads();
+    }
+    if (ok && (int)threadIdx.x < here) {
+        const pgx_ks_note q = notes[first + (int)threadIdx.x];
+        const pgx_ks_params p = *q.params;
+        pgx_ks_state st = *q.state;
+        float *o = out + q.dst;
+        if (use_lds) ks_run(ks_lds + (int)threadIdx.x * stride, p, st, o, q.start, q.frames, channels);
+        else ks_run(q.line + p.line_offset, p, st, o, q.start, q.frames, channels);
+        *q.state = st;
+    }
+    if (use_lds) {
+        __syncthreads();
+        for (int k = 0; k < here; ++k) {
+            const pgx_ks_note q = notes[first + k];
+            float *dst = q.line + q.params->line_offset;
+            const int n = q.params->n;
+            for (int x = threadIdx.x; x < n; x += kKsLanes) dst[x] = ks_lds[k * stride + x];
+        }
+    }
+}
+
+__global__ void __launch_bounds__(kKsLanes)
+k_karplus_score(float *out, int channels, const pgx_ks_note *notes, int count, int group, int max_line,
+                int lds_floats) {
+    extern __shared__ float ks_lds[];
+    ks_score_body(ks_lds, out, channels, notes, count, group, max_line, lds_floats);
+}
+
+__global__ void __launch_bounds__(kKsLanes)
+k_karplus_score_inline(float *out, int channels, KsInline notes, int count, int group, int max_line, int lds_floats) {
+    extern __shared__ float ks_lds[];
+    ks_score_body(ks_lds, out, channels, notes.n, count, group, max_line, lds_floats);
+}
+
 // ================================================================================================
 // AnalogOscPE
 // ================================================================================================
@@ -403,6 +469,31 @@ int pgx_karplus_strong(float *out, int64_t out_stride, int batch, int64_t start,
                            batch, start, n, channels, params, lines, state, max_line);
     }
     PGX_LAUNCH_CHECK("k_karplus_strong");
+    return PGX_OK;
+}
+
+int pgx_karplus_score(float *out, int channels, const pgx_ks_note *notes, int count, int group, int max_line,
+                      int notes_on_host) {
+    PGX_REQUIRE_INIT();
+    if (count <= 0) return PGX_OK;
+    PGX_CHECK_ARG(out && notes && channels >= 1 && group >= 1 && group <= kKsLanes && max_line >= 2 &&
+                      (!notes_on_host || count <= kKsInline),
+                  "pgx_karplus_score: bad argument");
+    const int grid = (int)pgx::ceil_div(count, group);
+    const int lanes = count < group ? count : group;
+    int64_t lds = (int64_t)lanes * max_line * (int64_t)sizeof(float);
+    if (lds > kKsLdsBytes) lds = kKsLdsBytes;
+    const int lds_floats = (int)(lds / (int64_t)sizeof(float));
+    if (notes_on_host) {
+        KsInline inl = {};
+        for (int i = 0; i < count; ++i) inl.n[i] = notes[i];
+        hipLaunchKernelGGL(k_karplus_score_inline, dim3(grid), dim3(kKsLanes), (size_t)lds, pgx::stream(), out,
+                           channels, inl, count, group, max_line, lds_floats);
+    } else {
+        hipLaunchKernelGGL(k_karplus_score, dim3(grid), dim3(kKsLanes), (size_t)lds, pgx::stream(), out, channels,
+                           notes, count, group, max_line, lds_floats);
+    }
+    PGX_LAUNCH_CHECK("k_karplus_score");
     return PGX_OK;
 }
 

@@ -175,6 +175,7 @@ _SIGNATURES = [
     ("pgx_allreduce_wait", _I, [_L]),
     ("pgx_allreduce_scalar_host", _I, [C.POINTER(_D), _I]),
     ("pgx_karplus_strong", _I, [_P, _L, _I, _L, _L, _I, _P, _P, _P, _I]),
+    ("pgx_karplus_score", _I, [_P, _I, _P, _I, _I, _I, _I]),
     ("pgx_analog_osc_workspace_bytes", _Z, [_L]),
     ("pgx_analog_osc_pure", _I, [_P, _L, _L, _I, _D, _I, _D, _D, _P]),
     ("pgx_analog_osc_stateful", _I, [_P, _L, _I, _D, _I, _D, _D, _P, _P, _I, _P, _P]),
@@ -189,6 +190,7 @@ _SIGNATURES = [
     ("pgx_dft_c2c", _I, [_P, _P, _L, _I, _I, _P, _P]),
     ("pgx_tralfam_workspace_bytes", _Z, [_L, _I]),
     ("pgx_tralfam", _I, [_P, _P, _L, _I, _P, _D, _P, _P]),
+    ("pgx_score_mix", _I, [_P, _L, _I, _P, _L, _P, _P, _L]),
 ]
 
 EXPORTED_SYMBOLS = [s[0] for s in _SIGNATURES]
@@ -212,6 +214,10 @@ GATE_PARAMS = np.dtype([("dt", "<f8"), ("phase", "<f8"), ("duty", "<f8")])
 KS_PARAMS = np.dtype([("line_offset", "<i8"), ("n", "<i4"), ("two_phase", "<i4"), ("switch_at", "<i8"),
                       ("rho", "<f4"), ("rho_damping", "<f4"), ("c", "<f4"), ("pad", "<f4")])
 KS_STATE = np.dtype([("r", "<i4"), ("ap_in", "<f4"), ("ap_out", "<f4"), ("pad", "<i4")])
+KS_NOTE = np.dtype([("params", "<u8"), ("line", "<u8"), ("state", "<u8"), ("start", "<i8"), ("frames", "<i8"),
+                    ("dst", "<i8")])
+SCORE_INLINE = 16          # PGX_SCORE_INLINE: tables of at most this many entries travel in the kernel arguments
+SCORE_SEG = np.dtype([("data", "<u8"), ("first", "<i8"), ("frames", "<i8")])
 NOISE_PARAMS = np.dtype([("state_hi", "<u8"), ("state_lo", "<u8"), ("inc_hi", "<u8"), ("inc_lo", "<u8"),
                          ("consumed", "<i8"), ("scaled", "<i4"), ("span", "<f4"), ("min_value", "<f4"), ("pad", "<i4")])
 NOISE_STATE = np.dtype([("pink", "<f4", (7,)), ("brown", "<f4")])

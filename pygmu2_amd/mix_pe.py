@@ -5,6 +5,9 @@ Inputs whose extent misses the requested window are skipped, as in the reference
 When every input is a structurally identical stateful voice graph the inputs are
 rendered as ONE batched launch per PE level (pygmu2_amd.voice_bank) and summed by a
 single kernel in the same float32 order -- same samples, far fewer launches.
+When the voice bank declines and at least two inputs are notes -- bounded on the timeline, as SequencePE places them --
+the score bank (pygmu2_amd.score_bank) renders each sounding note over its overlap with the block only and one kernel
+adds the pieces where they lie; the generic path below is what it must equal, and what PYGMU_SCORE_BANK=0 restores.
 Multi-GPU: pygmu2_amd.sharding.ShardedMixPE splits the inputs over ranks and reduces
 the partial mixes with RCCL.
 """
@@ -13,6 +16,7 @@ from __future__ import annotations
 
 import ctypes as C
 
+from . import score_bank as _score_bank
 from ._kernels import check, lib, new_output
 from .extent import Extent
 from .processing_element import ProcessingElement
@@ -30,6 +34,7 @@ class MixPE(ProcessingElement):
             raise ValueError("MixPE requires at least 2 inputs")
         self._inputs = list(inputs)
         self._bank = None            # lazily built voice bank (or False when not batchable)
+        self._score = None           # lazily built score bank (score_bank.py), asked only when the voice bank declines
 
     def inputs(self) -> list[ProcessingElement]:
         return self._inputs
@@ -67,6 +72,14 @@ class MixPE(ProcessingElement):
                 self._bank.set_mix_windows()
         return self._bank
 
+    def _score_bank(self):
+        """The score bank over bounded notes, or False (fewer than two notes; PYGMU_SCORE_BANK=0)."""
+        if not _score_bank.enabled():
+            return False
+        if self._score is None:
+            self._score = _score_bank.try_build_score(self._inputs) or False
+        return self._score
+
     def _read_ahead_condition(self) -> bool:
         # the skip rule below looks at the requested window; with bounded inputs a larger window changes it
         return all(pe.extent().start is None and pe.extent().end is None for pe in self._inputs)
@@ -78,6 +91,9 @@ class MixPE(ProcessingElement):
         bank = self._voice_bank()
         if bank:
             return bank.render_mix(start, duration)
+        score = self._score_bank()
+        if score:
+            return score.render_mix(self, start, duration)
 
         window = Extent(start, start + duration)
         snippets = [pe.render(start, duration) for pe in self._inputs
