@@ -338,7 +338,9 @@ int pgx_f32_to_pcm16(int16_t *out, const float *in, int64_t n_elems);
 int pgx_pcm16_to_f32(float *out, const int16_t *in, int64_t n_elems);
 
 /* ------------------------------------------------------------------ SpatialPE (section 8f rank 2)
- * SpatialAdapter.render (spatial_pe.py:94-144): M -> N channels. */
+ * SpatialAdapter.render (spatial_pe.py:94-144): M -> N channels.
+ * The three entry points below average channels as np.mean does a float32 row: fewer than 8 terms one after the
+ * other, 8 .. 128 terms on eight running sums joined pairwise; more than 128 source channels are refused. */
 int pgx_channel_adapt(float *out, const float *in, int64_t n, int src_channels, int out_channels);
 /* SpatialLinear / SpatialConstantPower.render (spatial_pe.py:179-214, 250-286): mono mix of the source
  * panned to stereo; azimuth in degrees, clipped to +-90; azimuth_stream: per-frame float32 or NULL. */

@@ -412,12 +412,33 @@ k_pcm16_to_f32(float *out, const int16_t *in, int64_t n) {
 
 // ------------------------------------------------------------------------------------------------
 // SpatialPE (spatial_pe.py:94-144, 179-214, 250-286): channel adaptation and stereo panning, float32
-// arithmetic like the reference's numpy expressions (np.mean of a float32 row: sequential float32 sum / n).
+// arithmetic like the reference's numpy expressions.  np.mean of a float32 row adds in numpy's blocked order: fewer
+// than 8 terms one after the other; 8 .. 128 (kRowMeanMax) terms on eight running sums r[j] += row[8 i + j], joined as
+// ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7)), the last n % 8 terms added to that one by one; then / n.  (Beyond
+// 128 terms numpy halves the row first: not restated here, the entry points refuse such rows.)
 // ------------------------------------------------------------------------------------------------
+constexpr int kRowMeanMax = 128;
+
 __device__ __forceinline__ float row_mean(const float *row, int from, int to) {
-    float acc = row[from];
-    for (int c = from + 1; c < to; ++c) acc = acc + row[c];
-    return acc / (float)(to - from);
+    const int n = to - from;
+    const float *a = row + from;
+    float acc;
+    if (n < 8) {
+        acc = a[0];
+        for (int c = 1; c < n; ++c) acc = acc + a[c];
+    } else {
+        float r[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) r[j] = a[j];
+        int i = 8;
+        for (; i + 8 <= n; i += 8) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) r[j] = r[j] + a[i + j];
+        }
+        acc = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
+        for (; i < n; ++i) acc = acc + a[i];
+    }
+    return acc / (float)n;
 }
 
 __global__ void __launch_bounds__(kBlock)
@@ -435,7 +456,7 @@ k_channel_adapt(float *out, const float *in, int64_t n, int src_ch, int out_ch) 
             y[0] = x[0]; y[1] = x[1]; y[2] = cs; y[3] = cs;
         } else if (src_ch == 4 && out_ch == 2) {
             y[0] = x[0]; y[1] = x[1];
-        } else if (out_ch > src_ch) {
+        } else if (out_ch >= src_ch) {                  // (as many: a copy, spatial_pe.py:104-105 -- no channels left to fold)
             for (int c = 0; c < src_ch; ++c) y[c] = x[c];
             for (int c = src_ch; c < out_ch; ++c) y[c] = x[src_ch - 1];
         } else {
@@ -483,6 +504,7 @@ int pgx_channel_adapt(float *out, const float *in, int64_t n, int src_channels, 
     PGX_REQUIRE_INIT();
     if (n <= 0) return PGX_OK;
     PGX_CHECK_ARG(out && in && src_channels >= 1 && out_channels >= 1, "pgx_channel_adapt: bad argument");
+    PGX_CHECK_ARG(src_channels <= kRowMeanMax, "pgx_channel_adapt: more than 128 source channels");
     hipLaunchKernelGGL(k_channel_adapt, dim3(pgx::grid_for(n, kBlock)), dim3(kBlock), 0, pgx::stream(), out, in, n,
                        src_channels, out_channels);
     PGX_LAUNCH_CHECK("k_channel_adapt");
@@ -494,6 +516,7 @@ int pgx_pan(float *out, const float *in, int64_t n, int src_channels, float azim
     PGX_REQUIRE_INIT();
     if (n <= 0) return PGX_OK;
     PGX_CHECK_ARG(out && in && src_channels >= 1, "pgx_pan: bad argument");
+    PGX_CHECK_ARG(src_channels <= kRowMeanMax, "pgx_pan: more than 128 source channels");
     hipLaunchKernelGGL(k_pan, dim3(pgx::grid_for(n, kBlock)), dim3(kBlock), 0, pgx::stream(), out, in, n,
                        src_channels, azimuth, azimuth_stream, constant_power ? 1 : 0);
     PGX_LAUNCH_CHECK("k_pan");
@@ -504,6 +527,7 @@ int pgx_mono_mean(float *out, const float *in, int64_t n, int src_channels) {
     PGX_REQUIRE_INIT();
     if (n <= 0) return PGX_OK;
     PGX_CHECK_ARG(out && in && src_channels >= 1, "pgx_mono_mean: bad argument");
+    PGX_CHECK_ARG(src_channels <= kRowMeanMax, "pgx_mono_mean: more than 128 source channels");
     hipLaunchKernelGGL(k_mono_mean, dim3(pgx::grid_for(n, kBlock)), dim3(kBlock), 0, pgx::stream(), out, in, n,
                        src_channels);
     PGX_LAUNCH_CHECK("k_mono_mean");

@@ -37,15 +37,16 @@ def array_data(n: int, channels: int, key: int) -> np.ndarray:
 def build_source(K, src):
     """One note source: an unbounded or array PE, cropped to its length when the spec says so."""
     t = src["type"]
+    wide = {"channels": src["channels"]} if "channels" in src else {}      # the oscillators: one column, repeated
     if t == "ks":
         kw = {"rho": src["rho"], "seed": src["seed"]}
         if "duration" in src:
             kw.update(duration=src["duration"], rho_damping=src["rho_damping"])
-        pe = K.KarplusStrongPE(src["freq"], **kw)
+        pe = K.KarplusStrongPE(src["freq"], **kw, **wide)
     elif t == "saw":
-        pe = K.BlitSawPE(src["freq"], amplitude=src["amp"])
+        pe = K.BlitSawPE(src["freq"], amplitude=src["amp"], **wide)
     elif t == "sine":
-        pe = K.SinePE(src["freq"], amplitude=src["amp"])
+        pe = K.SinePE(src["freq"], amplitude=src["amp"], **wide)
     elif t == "noise":
         pe = K.NoisePE(min_value=-src["amp"], max_value=src["amp"], seed=src["seed"])
     elif t == "array":

@@ -106,28 +106,35 @@ def _score_mix(lib, segments, frames, ch, inline):
 
 @pytest.mark.parametrize("ch", [1, 2])
 def test_score_mix_kernel_is_the_ordered_sum(ch):
+    check_score_mix_kernel(ch)
+
+
+def check_score_mix_kernel(ch, frames=10_000, count=300, edges=(1, 3, 9), crowd=40):
+    """pgx_score_mix against the ordered float32 sum: `count` segments over `frames` frames, some a frame either side
+    of the tile edges `edges`, `crowd` of them over the middle frame (tests/test_gpu_channels.py runs it at 3 and 5
+    channels with smaller counts)."""
     lib = device.ensure_init()
-    frames, tile = 10_000, score_bank.TILE
+    tile, mid = score_bank.TILE, frames // 2
     rng = np.random.default_rng(7 + ch)
 
     def seg(first, n):
         return int(first), rng.uniform(-1, 1, (int(n), ch)).astype(np.float32)
 
     assert not np.any(_score_mix(lib, [], frames, ch, False))                         # k = 0
-    one = [seg(123, 4567)]
+    one = [seg(123, min(4567, frames - 123))]
     for inline in (True, False):                                                      # k = 1, both table routes
         assert np.array_equal(_score_mix(lib, one, frames, ch, inline), ordered_sum(one, frames, ch))
     segs = [seg(0, 1), seg(frames - 1, 1), seg(0, 700), seg(frames - 333, 333), seg(0, frames)]
-    for t in (1, 3, 9):                                                               # one frame either side of a tile edge
+    for t in edges:                                                                   # one frame either side of a tile edge
         segs += [seg(t * tile - 500, 499), seg(t * tile - 500, 500), seg(t * tile - 500, 501), seg(t * tile, 1),
                  seg(t * tile - 1, 1), seg(t * tile - 1, 2)]
-    segs += [seg(5000 - j, 1 + j + (j * 7) % 90) for j in range(40)]                  # 40 segments cover frame 5000
-    while len(segs) < 300:
+    segs += [seg(mid - j, 1 + j + (j * 7) % 90) for j in range(crowd)]                # `crowd` segments cover frame `mid`
+    while len(segs) < count:
         first = int(rng.integers(0, frames))
         segs.append(seg(first, rng.integers(1, min(2500, frames - first) + 1)))
     order = rng.permutation(len(segs))
     segs = [segs[i] for i in order]
-    assert len(segs) == 300 and sum(f <= 5000 < f + len(d) for f, d in segs) >= 40
+    assert len(segs) == count and sum(f <= mid < f + len(d) for f, d in segs) >= crowd
     assert np.array_equal(_score_mix(lib, segs, frames, ch, False), ordered_sum(segs, frames, ch))
     few = segs[:device.SCORE_INLINE]
     assert np.array_equal(_score_mix(lib, few, frames, ch, True), ordered_sum(few, frames, ch))
@@ -136,13 +143,19 @@ def test_score_mix_kernel_is_the_ordered_sum(ch):
 # ---------------------------------------------------------------------------------------------- pgx_karplus_score
 @pytest.mark.parametrize("ch,group", [(1, 1), (1, 16), (2, 16), (1, 64), (2, 7)])
 def test_karplus_score_kernel_matches_one_string_at_a_time(ch, group):
+    check_karplus_score_kernel(ch, group)
+
+
+def check_karplus_score_kernel(ch, group, count=130):
+    """pgx_karplus_score against pgx_karplus_strong one string at a time, `count` strings (tests/test_gpu_channels.py
+    runs it at 3 and 5 channels with fewer strings)."""
     lib = device.ensure_init()
-    sr, count = 20_000, 130
+    sr, far = 20_000, min(77, count - 1)
     rng = np.random.default_rng(3)
     freqs = np.exp(rng.uniform(np.log(25.0), np.log(6000.0), count))
-    freqs[5], freqs[77] = 10_000.0, 1.0                     # N = 2 and N = 20 000 (80 KB: past the LDS path)
+    freqs[5], freqs[far] = 10_000.0, 1.0                    # N = 2 and N = 20 000 (80 KB: past the LDS path)
     geo = [ks_geometry(sr, f) for f in freqs]
-    assert geo[5][0] == 2 and geo[77][0] == 20_000
+    assert geo[5][0] == 2 and geo[far][0] == 20_000
     fixed = [1, 63, 64, 65, 129]
     calls = [np.array(fixed + list(rng.integers(1, 3001, count - len(fixed)))),
              np.array(list(rng.integers(1, 3001, count - len(fixed))) + fixed)]

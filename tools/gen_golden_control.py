@@ -162,6 +162,33 @@ def cases():
     add("patch_sh_slew_biquad", S("BiquadPE", source=S("BlitSawPE", frequency=110.0), frequency=cutoff, q=2.0),
         blocks_contig(0, [1024] * 8), keep_every=2)
     c += fuzz_cases()
+    c += channel_cases()
+    return c
+
+
+# ---------------------------------------------------------------------------------------------- 3, 4, 5, 8 channels
+def channel_cases():
+    """Sources of 3, 4, 5 and 8 different columns under SampleHoldPE / TrackHoldPE (a mono control: pgx_hold's vector
+    path; a control as wide as the source) and SlewLimiterPE (both modes) -- these PEs read channel 0 of a wider source
+    or control and give one channel, so it is the strides of the reads that change; FunctionGenPE with `channels` of as
+    many, pure and stateful.  Blocks of odd lengths from a negative start, state carried."""
+    c = []
+    odd = blocks_contig(-37, [1, 17, 257, 1000])
+    vib = affine(S("SinePE", frequency=5.0), 20.0, 440.0)
+    for ch in (3, 4, 5, 8):
+        def add(name, graph, blocks=odd):
+            c.append({"name": f"ch{ch}_{name}", "sr": SR, "graph": graph, "blocks": blocks})
+        add("sh_mono_control", SH(noise(200 + ch, 1300, ch), S("PeriodicTrigger", hz=375.0), 0.1))
+        add("sh_wide_control", SH(noise(210 + ch, 1300, ch), affine(noise(220 + ch, 1300, ch), 1.0, -0.6), 0.1))
+        add("th_mono_control", TH(noise(230 + ch, 1300, ch), S("PeriodicGate", frequency=200.0, duty_cycle=0.3), 0.1))
+        add("th_wide_control", TH(noise(240 + ch, 1300, ch), affine(noise(250 + ch, 1300, ch), 1.0, 0.5), 0.1))
+        add("slew_linear", SL(noise(260 + ch, 1300, ch), 2000.0, 500.0, "linear"))
+        add("slew_exponential", SL(noise(270 + ch, 1300, ch), 3000.0, 800.0, "exponential"))
+        add("fg_pure_sawtooth", FG(441.0, 0.25, 0.1, "sawtooth", ch))
+        add("fg_pure_rectangle", FG(441.0, 0.3, 0.37, "rectangle", ch))
+        add("fg_stateful_sawtooth", FG(vib, 0.3, 0.0, "sawtooth", ch), blocks_contig(0, [1, 17, 257, 1000]))
+        add("fg_stateful_rectangle", FG(S("ConstantPE", value=750.0), 0.25, 0.0, "rectangle", ch),
+            blocks_contig(0, [1, 17, 257, 1000]))
     return c
 
 

@@ -133,6 +133,28 @@ def cases():
     add("ex20_jog_shuttle_48000", S("CropPE", source=S("GainPE", source=jog, gain=0.8), start=0, duration=48000),
         [[0, 48000]])
     c += fuzz_cases()
+    c += channel_cases()
+    return c
+
+
+# ---------------------------------------------------------------------------------------------- 3, 4, 5, 8 channels
+def channel_cases():
+    """Tables and tapes of 3, 4, 5 and 8 different columns (a float4 straddles frames at 3, lies inside one at 5; a
+    frame is one or two float4s at 4 and 8): every out-of-bounds mode x interpolation of WavetablePE, TimeWarpPE at a
+    scalar and at a PE rate, in blocks of odd lengths that carry the head from one to the next."""
+    c = []
+    swing = affine(S("SinePE", frequency=97.0), 200.0, 128.0)               # [-72, 328] over a table on [0, 256)
+    for ch in (3, 4, 5, 8):
+        for mode in ("zero", "clamp", "wrap"):
+            for interp in ("linear", "cubic"):
+                c.append({"name": f"ch{ch}_wt_{mode}_{interp}", "sr": SR, "blocks": blocks_contig(-37, [1, 17, 257]),
+                          "graph": WT(noise(100 + ch, 256, ch), swing, interp, mode)})
+        tape = S("DelayPE", source=noise(110 + ch, 3000, ch), delay=-1500)
+        ramp = S("PiecewisePE", points=[[0, 0.3], [3000, 1.7]], extend_mode="hold_both")
+        c.append({"name": f"ch{ch}_tw_rate_1.5_cubic", "sr": SR, "blocks": blocks_contig(0, [1, 17, 257]),
+                  "graph": TW(tape, 1.5, "cubic")})
+        c.append({"name": f"ch{ch}_tw_pe_rate", "sr": SR, "blocks": blocks_contig(0, [1, 17, 257]),
+                  "graph": TW(tape, ramp)})
     return c
 
 

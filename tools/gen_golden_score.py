@@ -123,6 +123,16 @@ def cases():
     add("negative_starts", "sequence", "non_overlap", negative, "bits")
     add("single_pair", "sequence", "overlap", score(11, 1, ks), "bits", form="bare")
     add("mozart_handbuilt", "handbuilt", None, mozart(), "bits")
+    # ---- notes of 3 and 5 channels (arrays: every column its own; plucks and sines: one column repeated), both modes
+    def wide(make, channels):
+        def made(rng, i, length):
+            return dict(make(rng, i, length), channels=channels)
+        return made
+    for ch, modes in ((3, ("overlap", "non_overlap")), (5, ("overlap",))):
+        for mode in modes:
+            add(f"ch{ch}_array_{mode}", "sequence", mode, score(20 + ch, 8, wide(array, ch), total=1500), "bits")
+            add(f"ch{ch}_pluck_{mode}", "sequence", mode, score(30 + ch, 8, wide(ks, ch), total=1500), "bits")
+            add(f"ch{ch}_sine_{mode}", "sequence", mode, score(40 + ch, 8, wide(tone("sine"), ch), total=1500), "tol")
     return c
 
 
@@ -225,7 +235,7 @@ class _Files(dict):
 
 def build_case_checked(K, case):
     pe = S.build_case(K, case)
-    assert pe.channel_count() in (1, 2), case["name"]
+    assert pe.channel_count() in (1, 2, 3, 5), case["name"]
     return pe
 
 
@@ -233,7 +243,7 @@ def check_sum_of_notes(K, case, pe, renderer, whole):
     """The reference's SequencePE == the float32 sum, in sorted-input order, of each note rendered alone over only its
     own length (OVERLAP) or up to the next start (NON_OVERLAP)."""
     w0, wn = case["patterns"]["whole"][0]
-    want = np.zeros((wn, 1), dtype=np.float32)
+    want = np.zeros((wn, whole.shape[1]), dtype=np.float32)
     pairs = pe._pairs
     fresh = S.build_case(K, case)._pairs
     for k, ((_, start), (src, _)) in enumerate(zip(pairs, fresh)):

@@ -145,6 +145,16 @@ def cases():
     add("set_extent_open_end", "set_extent", noise(300), [[-100, 700], [90, 20]], start=100, duration=None,
         extend_mode="hold_both")
     add("set_extent_open_both", "set_extent", noise(300), [[-100, 700]], start=None, duration=None, extend_mode="zero")
+
+    # ---- 3, 4, 5 and 8 channels (every column its own noise): a float4 straddles frames at 3, lies inside one at 5, a
+    # frame is one or two float4s at 4 and 8.  499 frames: no power of two, the arbitrary-length transform per channel
+    for ch in (3, 4, 5, 8):
+        add(f"ch{ch}_tralfam_499", "plain", noise(499, ch), whole(499), seed=SEEDS[ch % len(SEEDS)],
+            normalize_peak=None if ch % 2 else 0.5)
+        add(f"ch{ch}_slice_both", "slice", noise(600, ch), [[-100, 500]], sr=1000, start=150, duration=300,
+            fade_in_seconds=0.05, fade_out_seconds=0.08)
+        add(f"ch{ch}_set_extent_hold_both", "set_extent", noise(300, ch), [[-100, 300], [200, 200]], start=50, duration=200,
+            extend_mode="hold_both")
     for case in c:
         if case["graph"] in ("slice", "set_extent"):
             faded = case["graph"] == "slice" and case["duration"] > 0 and (
