@@ -33,9 +33,11 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 sys.path.insert(0, ROOT)
+sys.path.insert(1, os.path.join(ROOT, "tests"))
 REF = "/root/reference/src/pygmu2"
 
-from oracle.golden_cases import cases, materialize_array  # noqa: E402
+from oracle import spec_builder  # noqa: E402
+from oracle.golden_cases import S, cases  # noqa: E402
 
 
 def load_reference():
@@ -65,138 +67,43 @@ def load_reference():
                  "reverb_pe", "assets", "spatial_pe", "loop_pe", "window_pe", "conversions", "dynamics_pe",
                  "compressor_pe", "karplus_strong_pe", "analog_osc_pe"):
         mods[name] = importlib.import_module(f"pygmu2.{name}")
+    mods["K"] = reference_namespace(mods)
     return mods
 
 
-def build(spec, M, shared=None):
-    """SPEC -> reference PE instance (a node with `"share": <name>` is one instance wherever the name appears)."""
-    shared = {} if shared is None else shared
-    name = spec.get("share")
-    if name is not None and name in shared:
-        return shared[name]
-    pe = _build(spec, M, shared)
-    if name is not None:
-        shared[name] = pe
-    return pe
+# modules beside load_reference()'s that the newer families' generators read classes from
+EXTRA_MODULES = ("timewarp_pe", "sample_hold_pe", "track_hold_pe", "slew_limiter_pe", "function_gen_pe", "noise_pe",
+                 "tralfam_pe", "slice_pe", "set_extent_pe", "sequence_pe")
 
 
-def _build(spec, M, shared):
-    kind = spec["pe"]
-    kw = {}
-    for k, v in spec.items():
-        if k in ("pe", "share"):
-            continue
-        if isinstance(v, dict) and "pe" in v:
-            kw[k] = build(v, M, shared)
-        elif isinstance(v, dict):
-            kw[k] = materialize_array(v)
-        elif k == "inputs":
-            kw[k] = [build(s, M, shared) for s in v]
-        else:
-            kw[k] = v
-    E = M["extent"].ExtendMode
-    if "extend_mode" in kw:
-        kw["extend_mode"] = E(kw["extend_mode"])
-    if kind == "ConstantPE":
-        return M["constant_pe"].ConstantPE(**kw)
-    if kind == "IdentityPE":
-        return M["identity_pe"].IdentityPE(**kw)
-    if kind == "DiracPE":
-        return M["dirac_pe"].DiracPE(**kw)
-    if kind == "ArrayPE":
-        return M["array_pe"].ArrayPE(**kw)
-    if kind == "CropPE":
-        return M["crop_pe"].CropPE(**kw)
-    if kind == "SinePE":
-        return M["sine_pe"].SinePE(**kw)
-    if kind == "GainPE":
-        return M["gain_pe"].GainPE(**kw)
-    if kind == "MixPE":
-        return M["mix_pe"].MixPE(*kw["inputs"])
-    if kind == "BiquadPE":
-        if "mode" in kw:
-            kw["mode"] = M["biquad_pe"].BiquadMode(kw["mode"])
-        return M["biquad_pe"].BiquadPE(**kw)
-    if kind == "BlitSawPE":
-        return M["blit_saw_pe"].BlitSawPE(**kw)
-    if kind == "SuperSawPE":
-        return M["super_saw_pe"].SuperSawPE(**kw)
-    if kind == "LadderPE":
-        if "mode" in kw:
-            kw["mode"] = M["ladder_pe"].LadderMode(kw["mode"])
-        return M["ladder_pe"].LadderPE(**kw)
-    if kind == "CombPE":
-        return M["comb_pe"].CombPE(**kw)
-    if kind == "AdsrGatedPE":
-        return M["adsr_pe"].AdsrGatedPE(**kw)
-    if kind == "AdsrTriggeredPE":
-        return M["adsr_pe"].AdsrTriggeredPE(**kw)
-    if kind == "PeriodicGate":
-        return M["periodic_gate"].PeriodicGate(**kw)
-    if kind == "PeriodicTrigger":
-        return M["periodic_trigger"].PeriodicTrigger(**kw)
-    if kind == "ConvolvePE":
-        return M["convolve_pe"].ConvolvePE(kw.pop("src"), kw.pop("fir"), **kw)
-    if kind == "SVFilterPE":
-        if "mode" in kw:
-            kw["mode"] = M["biquad_pe"].BiquadMode(kw["mode"])
-        return M["svfilter_pe"].SVFilterPE(**kw)
-    if kind == "EnvelopePE":
-        if "mode" in kw:
-            kw["mode"] = M["envelope_pe"].DetectionMode(kw["mode"])
-        return M["envelope_pe"].EnvelopePE(**kw)
-    if kind == "SpatialPE":
-        sp = M["spatial_pe"]
-        method = kw["method"]
-        if method == "adapter":
-            meth = sp.SpatialAdapter(kw["channels"])
-        elif method == "linear":
-            meth = sp.SpatialLinear(kw["azimuth"])
-        elif method == "constant_power":
-            meth = sp.SpatialConstantPower(kw["azimuth"])
-        else:
-            meth = sp.SpatialHRTF(kw["azimuth"], kw.get("elevation", 0.0))
-            name = sp.SpatialHRTF.hrtf_filename_for(meth.azimuth, meth.elevation)
-            import wave
-            with wave.open(os.path.join(ROOT, "tests", "golden", "kemar", name), "rb") as w:
-                pcm = np.frombuffer(w.readframes(w.getnframes()), dtype="<i2").reshape(-1, w.getnchannels())
-                # libsndfile's PCM16 -> float32 (x / 32768), what sf.read(dtype="float32") returns
-                meth._ir_cache[name] = ((pcm.astype(np.float32) * np.float32(1.0 / 32768.0)), w.getframerate())
-        return sp.SpatialPE(kw["source"], method=meth)
-    if kind == "DelayPE":
-        if "interpolation" in kw:
-            kw["interpolation"] = M["wavetable_pe"].InterpolationMode(kw["interpolation"])
-        return M["delay_pe"].DelayPE(**kw)
-    if kind == "PiecewisePE":
-        kw["points"] = [(int(t), float(v)) for t, v in kw["points"]]
-        return M["piecewise_pe"].PiecewisePE(**kw)
-    if kind == "TriggerRestartPE":
-        return M["trigger_restart_pe"].TriggerRestartPE(kw["trigger"], kw["src"])
-    if kind == "ReverbPE":
-        return M["reverb_pe"].ReverbPE(kw.pop("source"), kw.pop("ir"), kw.pop("mix", 0.5), **kw)
-    if kind == "LoopPE":
-        return M["loop_pe"].LoopPE(kw.pop("source"), **kw)
-    if kind == "WindowPE":
-        if "mode" in kw:
-            kw["mode"] = M["window_pe"].WindowMode(kw["mode"])
-        return M["window_pe"].WindowPE(**kw)
-    if kind == "DynamicsPE":
-        if "mode" in kw:
-            kw["mode"] = M["dynamics_pe"].DynamicsMode(kw["mode"])
-        return M["dynamics_pe"].DynamicsPE(**kw)
-    if kind in ("CompressorPE", "LimiterPE", "ExpanderPE"):
-        if "detection" in kw:
-            kw["detection"] = M["envelope_pe"].DetectionMode(kw["detection"])
-        return getattr(M["compressor_pe"], kind)(kw.pop("source"), **kw)
-    if kind == "CachePE":
-        return M["cache_pe"].CachePE(kw["source"])
-    if kind == "TransformPE":
-        return M["transform_pe"].TransformPE(kw["source"], func=numpy_func(kw["ops"]), name="ops")
-    if kind == "KarplusStrongPE":
-        return M["karplus_strong_pe"].KarplusStrongPE(**kw)
-    if kind == "AnalogOscPE":
-        return M["analog_osc_pe"].AnalogOscPE(**kw)
-    raise KeyError(kind)
+def reference_namespace(M):
+    """The reference's classes and enums as the flat namespace oracle/spec_builder.py builds over (every capitalised
+    name of load_reference()'s modules and of EXTRA_MODULES), with the builder's hooks."""
+    K = types.SimpleNamespace()
+    for mod in list(M.values()) + [importlib.import_module(f"pygmu2.{name}") for name in EXTRA_MODULES]:
+        for name, value in vars(mod).items():
+            if name[:1].isupper() and getattr(value, "__module__", None) == mod.__name__:
+                setattr(K, name, value)
+    K.transform_func = numpy_func
+    K.hrtf = lambda azimuth, elevation: hrtf_method(K.SpatialHRTF, azimuth, elevation)
+    return K
+
+
+def hrtf_method(SpatialHRTF, azimuth, elevation):
+    """A SpatialHRTF whose IR cache holds the fixture WAV it would load (the reference reads it through soundfile)."""
+    import wave
+    meth = SpatialHRTF(azimuth, elevation)
+    name = SpatialHRTF.hrtf_filename_for(meth.azimuth, meth.elevation)
+    with wave.open(os.path.join(ROOT, "tests", "golden", "kemar", name), "rb") as w:
+        pcm = np.frombuffer(w.readframes(w.getnframes()), dtype="<i2").reshape(-1, w.getnchannels())
+        # libsndfile's PCM16 -> float32 (x / 32768), what sf.read(dtype="float32") returns
+        meth._ir_cache[name] = ((pcm.astype(np.float32) * np.float32(1.0 / 32768.0)), w.getframerate())
+    return meth
+
+
+def build(spec, M, shared=None, on_make=None):
+    """SPEC -> reference PE instance: oracle/spec_builder.py's table over the namespace of load_reference()."""
+    return spec_builder.build(spec, M["K"], shared, on_make)
 
 
 def numpy_func(ops):
@@ -225,13 +132,76 @@ def numpy_func(ops):
 
 
 def has_kind(spec, kind):
-    if isinstance(spec, dict):
-        if spec.get("pe") == kind:
-            return True
-        return any(has_kind(v, kind) for v in spec.values())
-    if isinstance(spec, list):
-        return any(has_kind(v, kind) for v in spec)
+    return kind in spec_builder.kinds_of(spec)
+
+
+def render_case(case, M):
+    """Every block of a case (the format of oracle/golden_cases.py) through the reference's classes, in a started
+    NullRenderer -> list of float32 arrays."""
+    M["config"].set_sample_rate(case["sr"])
+    pe = build(case["graph"], M)
+    r = M["null_renderer"].NullRenderer(sample_rate=case["sr"])
+    r.set_source(pe)
+    # A reference ConvolvePE cannot be start()ed (its _reset_state drops the tail
+    # that _ensure_filter_prepared never re-creates, SURVEY.md section 8 a14); the
+    # reference's own tests render it un-started, so do the same.
+    if not (has_kind(case["graph"], "ConvolvePE") or has_kind(case["graph"], "ReverbPE")):
+        r.start()
+    outs = []
+    for s, n in case["blocks"]:
+        data = pe.render(int(s), int(n)).data
+        assert data.dtype == np.float32 and data.shape[0] == n, (case["name"], data.dtype, data.shape)
+        outs.append(np.ascontiguousarray(data))
+    return outs
+
+
+# ---------------------------------------------------------------------------------------------- shared by tools/gen_golden_*.py
+def affine(src, scale, offset):
+    return S("TransformPE", source=src, ops=[["affine", scale, offset]])
+
+
+def sums_exact(values):
+    """True when every sum of any of these float64 values, in any order, is exact: all are multiples of 2^-q and the
+    sum of their magnitudes times 2^q stays below 2^52."""
+    values = np.asarray(values, dtype=np.float64)
+    if not np.all(np.isfinite(values)):
+        return False
+    for q in range(0, 41):
+        scaled = values * 2.0 ** q
+        if np.all(scaled == np.round(scaled)):
+            return float(np.sum(np.abs(scaled))) < 2.0 ** 52
     return False
+
+
+def render_reference(case, M, kinds, reset=None, render=None):
+    """A case with lifecycle "ops" through the reference's classes, by tests/fixture_harness.render_blocks
+    -> (blocks, root PE, its PEs of `kinds` in construction order).  reset(made): what a "reset" op does (reset_state()
+    of every one of them by default); render(pe, made, start, n): another way to pull one block."""
+    import fixture_harness as H
+    made = []
+    pe = build(case["graph"], M, on_make=lambda kind, node: made.append(node) if kind in kinds else None)
+    outs = H.render_blocks(pe, case["sr"], case["blocks"], case.get("ops"), lambda: (reset or H.reset_all)(made),
+                           renderer=M["null_renderer"].NullRenderer(sample_rate=case["sr"]),
+                           render=render and (lambda s, n: render(pe, made, s, n)))
+    return outs, pe, made
+
+
+def describe(pe):
+    """What the reference says about a PE, for the host-side tests."""
+    ext = pe.extent()
+    return {"repr": repr(pe), "extent": [ext.start, ext.end], "pure": bool(pe.is_pure()),
+            "channels": pe.channel_count(), "inputs": [type(i).__name__ for i in pe.inputs()]}
+
+
+def write_fixture(family, doc, arrays):
+    """tests/golden/<family>_cases.json and <family>.npz."""
+    import fixture_harness as H
+    cases_path, npz_path = H.paths(family)
+    with open(cases_path, "w") as fh:
+        json.dump(doc, fh, indent=1)
+    np.savez_compressed(npz_path, **arrays)
+    print(npz_path, os.path.getsize(npz_path), "bytes,", sum(a.size for a in arrays.values()), "samples;", cases_path,
+          os.path.getsize(cases_path), "bytes")
 
 
 def main():
@@ -239,20 +209,9 @@ def main():
     out = {}
     case_list = cases()
     for case in case_list:
-        M["config"].set_sample_rate(case["sr"])
-        pe = build(case["graph"], M)
-        r = M["null_renderer"].NullRenderer(sample_rate=case["sr"])
-        r.set_source(pe)
-        # A reference ConvolvePE cannot be start()ed (its _reset_state drops the tail
-        # that _ensure_filter_prepared never re-creates); the
-        # reference's own tests render it un-started, so do the same.
-        if not (has_kind(case["graph"], "ConvolvePE") or has_kind(case["graph"], "ReverbPE")):
-            r.start()
-        for i, (s, n) in enumerate(case["blocks"]):
-            data = pe.render(int(s), int(n)).data
-            assert data.dtype == np.float32 and data.shape[0] == n, (case["name"], data.dtype, data.shape)
-            if i in case["keep"]:
-                out[f"{case['name']}/{i}"] = np.ascontiguousarray(data)
+        outs = render_case(case, M)
+        for i in case["keep"]:
+            out[f"{case['name']}/{i}"] = outs[i]
         print(f"{case['name']:36s} blocks={len(case['blocks'])}")
     gdir = os.path.join(ROOT, "tests", "golden")
     os.makedirs(gdir, exist_ok=True)

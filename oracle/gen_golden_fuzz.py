@@ -32,7 +32,7 @@ ROOT = os.path.dirname(HERE)
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
-from oracle.gen_golden import build, has_kind, load_reference  # noqa: E402
+from oracle.gen_golden import load_reference, render_case  # noqa: E402
 
 N_OLD = 100           # seeds 0..99 of test_gpu_fuzz._graph
 N_SHORT = 150         # short-block seeds of the new generator
@@ -125,9 +125,9 @@ def corpus():
     return out + hand
 
 
-def choose_keep(outs):
+def choose_keep(outs, budget=BUDGET):
     """Blocks from the last backwards while they fit the budget; the smallest block if none does."""
-    keep, left = [], BUDGET
+    keep, left = [], budget
     for i in range(len(outs) - 1, -1, -1):
         size = outs[i].size
         if size <= left:
@@ -154,18 +154,7 @@ def main():
     M = load_reference()
     arrays, stored = {}, []
     for case in corpus():
-        M["config"].set_sample_rate(case["sr"])
-        pe = build(case["graph"], M)
-        r = M["null_renderer"].NullRenderer(sample_rate=case["sr"])
-        r.set_source(pe)
-        # as oracle/gen_golden.py: a reference ConvolvePE cannot be start()ed
-        if not (has_kind(case["graph"], "ConvolvePE") or has_kind(case["graph"], "ReverbPE")):
-            r.start()
-        outs = []
-        for s, n in case["blocks"]:
-            data = pe.render(int(s), int(n)).data
-            assert data.dtype == np.float32 and data.shape[0] == n, (case["name"], data.dtype, data.shape)
-            outs.append(np.ascontiguousarray(data))
+        outs = render_case(case, M)
         case["keep"] = choose_keep(outs)
         for i in case["keep"]:
             arrays[f"{case['name']}/{i}"] = outs[i]

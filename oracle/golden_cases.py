@@ -14,6 +14,7 @@ The same SPEC is interpreted three ways:
   * oracle/gen_golden.py      -> the reference's own PE classes (golden outputs)
   * oracle/graph_eval.py      -> the CPU oracle functions
   * tests/spec_build.py       -> pygmu2_amd PE classes (the HIP product path)
+The first and the last are oracle/spec_builder.py's one table over two namespaces of classes.
 
 Blocks are rendered in order on one started graph, so contiguous blocks exercise the
 carried state and gaps exercise the reset-on-discontinuity rules.

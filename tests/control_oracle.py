@@ -1,99 +1,24 @@
 """SampleHoldPE / TrackHoldPE / SlewLimiterPE / FunctionGenPE on the CPU: numpy restatements of the four `_render`s
 (the reference's operations in the reference's order: a sequential walk for the holds and the slew limiter,
-sequential np.cumsum for the generator's phase and np.sum for the carried one), the fixture loader, and the graph
-builder shared by the fixture generator (tools/gen_golden_control.py, over the reference's classes) and the tests
-(over pygmu2_amd's).
+sequential np.cumsum for the generator's phase and np.sum for the carried one), shared by the fixture generator
+(tools/gen_golden_control.py, over the reference's classes) and the tests (over pygmu2_amd's).
 
 Graphs are golden-case SPECs (oracle/golden_cases.py) with four more kinds:
     {"pe": "SampleHoldPE", "source": SPEC, "trigger": SPEC, "initial_value": number}
     {"pe": "TrackHoldPE", "source": SPEC, "gate": SPEC, "initial_value": number}
     {"pe": "SlewLimiterPE", "source": SPEC, "rise_rate": number, "fall_rate": number | null, "mode": "linear"|"exponential"}
     {"pe": "FunctionGenPE", "frequency" / "duty_cycle" / "phase": number | SPEC, "waveform": ..., "channels": int}
-Every other kind is evaluated by oracle/graph_eval.py (ControlNode derives from its Node) and built by the caller's
-builder for the existing kinds."""
+Every other kind is evaluated by oracle/graph_eval.py (ControlNode derives from its Node); oracle/spec_builder.py builds
+all of them, and tests/fixture_harness.py loads the fixture and holds the bounds."""
 
 from __future__ import annotations
-
-import json
-import os
 
 import numpy as np
 
 from oracle.graph_eval import INF, Node, _isect
-
-GOLDEN_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-CASES_PATH = os.path.join(GOLDEN_DIR, "control_cases.json")
-NPZ_PATH = os.path.join(GOLDEN_DIR, "control.npz")
+from oracle.spec_builder import is_spec
 
 NEW_KINDS = ("SampleHoldPE", "TrackHoldPE", "SlewLimiterPE", "FunctionGenPE")
-PEAK_BOUND = 1e-6          # tests/playback_gpu_common.py: re-associated float64 sums, max abs error <= 1e-6 * peak
-
-
-def load_cases():
-    with open(CASES_PATH) as f:
-        cases = json.load(f)
-    return cases, np.load(NPZ_PATH)
-
-
-def stored_blocks(case):
-    k = int(case.get("keep_every", 1))
-    return [i for i in range(len(case["blocks"])) if i % k == 0]
-
-
-def split_blocks(case, flat):
-    """The fixture's concatenated samples -> {block index: samples} for the stored blocks."""
-    out, at = {}, 0
-    for i in stored_blocks(case):
-        n = int(case["blocks"][i][1])
-        out[i] = flat[at:at + n]
-        at += n
-    assert at == len(flat)
-    return out
-
-
-# ---------------------------------------------------------------------------------------------- graphs
-def is_spec(v):
-    return isinstance(v, dict) and "pe" in v
-
-
-def build_graph(spec, build_existing, make_new):
-    """SPEC -> PE instance, bottom-up.  build_existing(spec) builds a node of an existing kind whose PE-valued
-    parameters are already instances; make_new(kind, kwargs) constructs one of the four new kinds (mode still a
-    string)."""
-    node = {}
-    for k, v in spec.items():
-        if is_spec(v):
-            node[k] = build_graph(v, build_existing, make_new)
-        elif k == "inputs":
-            assert not any(_mentions_new(s) for s in v), "a MixPE input may not hold one of the new kinds"
-            node[k] = v
-        else:
-            node[k] = v
-    if spec["pe"] in NEW_KINDS:
-        return make_new(spec["pe"], {k: v for k, v in node.items() if k != "pe"})
-    return build_existing(node)
-
-
-def _mentions_new(spec):
-    if not is_spec(spec):
-        return False
-    return spec["pe"] in NEW_KINDS or any(
-        _mentions_new(v) or (k == "inputs" and any(_mentions_new(s) for s in v)) for k, v in spec.items())
-
-
-def make_with(SampleHoldPE, TrackHoldPE, SlewLimiterPE, SlewMode, FunctionGenPE):
-    def make_new(kind, kw):
-        kw = dict(kw)
-        if kind == "SampleHoldPE":
-            return SampleHoldPE(kw.pop("source"), kw.pop("trigger"), **kw)
-        if kind == "TrackHoldPE":
-            return TrackHoldPE(kw.pop("source"), kw.pop("gate"), **kw)
-        if kind == "SlewLimiterPE":
-            if "mode" in kw:
-                kw["mode"] = SlewMode(kw["mode"])
-            return SlewLimiterPE(kw.pop("source"), **kw)
-        return FunctionGenPE(**kw)
-    return make_new
 
 
 # ---------------------------------------------------------------------------------------------- the four renders

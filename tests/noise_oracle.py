@@ -1,5 +1,5 @@
-"""NoisePE on the CPU, twice over, plus the fixture loader and graph plumbing shared by the fixture generator
-(tools/gen_golden_noise.py, over the reference's classes) and the tests (over pygmu2_amd's).
+"""NoisePE on the CPU, twice over, shared by the fixture generator (tools/gen_golden_noise.py, over the reference's
+classes) and the tests (over pygmu2_amd's).
 
 (a) The numpy restatement (`NoiseStream`): the reference's draws (np.random.default_rng(seed).uniform(-1, 1, n) as
     float32) and its PINK / BROWN loops and range scaling as the float32 operations that numpy >= 2 makes of them, one
@@ -16,30 +16,14 @@ oracle.graph_eval.Node) and rebuilds its children as NoiseNodes."""
 
 from __future__ import annotations
 
-import json
-import os
-
 import numpy as np
 
 import control_oracle as C
-from control_oracle import PEAK_BOUND, is_spec, split_blocks, stored_blocks      # noqa: F401  (shared with the tests)
 from oracle.graph_eval import INF
-
-GOLDEN_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-CASES_PATH = os.path.join(GOLDEN_DIR, "noise_cases.json")
-NPZ_PATH = os.path.join(GOLDEN_DIR, "noise.npz")
+from oracle.spec_builder import is_spec, kinds_of      # noqa: F401  (kinds_of: shared with the tests)
 
 KIND = "NoisePE"
 MODES = ("white", "pink", "brown")
-# tests/test_gpu_fuzz.py: what a graph with a filter or an envelope in it is held to, per block
-REL_TOL = 1e-5
-ABS_FLOOR = 1e-6
-
-
-def load_cases():
-    with open(CASES_PATH) as f:
-        cases = json.load(f)
-    return cases, np.load(NPZ_PATH)
 
 
 # ---------------------------------------------------------------------------------------------- (a) the restatement
@@ -174,60 +158,7 @@ def numpy_draws(seed, offset, n):
     return np.random.Generator(bit_gen).uniform(-1.0, 1.0, size=n).astype(F)
 
 
-# ---------------------------------------------------------------------------------------------- graphs
-def mentions(spec, kind=KIND):
-    if isinstance(spec, dict):
-        return spec.get("pe") == kind or any(mentions(v, kind) for v in spec.values())
-    if isinstance(spec, list):
-        return any(mentions(v, kind) for v in spec)
-    return False
-
-
-def kinds_of(spec, out=None):
-    out = set() if out is None else out
-    if isinstance(spec, dict):
-        if "pe" in spec:
-            out.add(spec["pe"])
-        for v in spec.values():
-            kinds_of(v, out)
-    elif isinstance(spec, list):
-        for v in spec:
-            kinds_of(v, out)
-    return out
-
-
-def build_graph(spec, build_existing, make_new, make_mix):
-    """control_oracle.build_graph's shape, with NoisePE among the new kinds and MixPE inputs built here too:
-    build_existing(node) builds a node of an existing kind whose PE-valued parameters are already instances (a sub-graph
-    without any new kind is handed to it whole), make_new(kind, kwargs) one of the new kinds, make_mix(inputs) a MixPE."""
-    if not (mentions(spec) or any(mentions(spec, k) for k in C.NEW_KINDS)):
-        return build_existing(spec)
-    node = {}
-    for k, v in spec.items():
-        if is_spec(v):
-            node[k] = build_graph(v, build_existing, make_new, make_mix)
-        elif k == "inputs":
-            node[k] = [build_graph(s, build_existing, make_new, make_mix) for s in v]
-        else:
-            node[k] = v
-    if spec["pe"] == KIND or spec["pe"] in C.NEW_KINDS:
-        return make_new(spec["pe"], {k: v for k, v in node.items() if k != "pe"})
-    if spec["pe"] == "MixPE":
-        return make_mix(node["inputs"])
-    return build_existing(node)
-
-
-def make_with(NoisePE, NoiseMode, make_control):
-    def make_new(kind, kw):
-        if kind != KIND:
-            return make_control(kind, kw)
-        kw = dict(kw)
-        if "mode" in kw:
-            kw["mode"] = NoiseMode(kw["mode"])
-        return NoisePE(**kw)
-    return make_new
-
-
+# ---------------------------------------------------------------------------------------------- graph evaluation
 class NoiseNode(C.ControlNode):
     """control_oracle.ControlNode plus the kind NoisePE, at any depth of the graph."""
 

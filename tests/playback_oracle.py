@@ -1,95 +1,23 @@
 """WavetablePE / TimeWarpPE on the CPU: numpy restatements of the two `_render`s and of interpolated_lookup (the
 reference's operations in the reference's order: sequential np.cumsum for the positions, np.sum for the carried head),
-the fixture loader, and the graph builder shared by the fixture generator (tools/gen_golden_playback.py, over the
-reference's classes) and the tests (over pygmu2_amd's).
+shared by the fixture generator (tools/gen_golden_playback.py, over the reference's classes) and the tests (over
+pygmu2_amd's).
 
 Graphs are golden-case SPECs (oracle/golden_cases.py) with two more kinds:
     {"pe": "WavetablePE", "wavetable": SPEC, "indexer": SPEC, "interpolation": "linear"|"cubic",
      "out_of_bounds": "zero"|"clamp"|"wrap"}
     {"pe": "TimeWarpPE", "source": SPEC, "rate": number | SPEC, "interpolation": ...}
-Every other kind is evaluated by oracle/graph_eval.py (PlaybackNode derives from its Node) and built by the caller's
-builder for the existing kinds."""
+Every other kind is evaluated by oracle/graph_eval.py (PlaybackNode derives from its Node); oracle/spec_builder.py builds
+all of them, and tests/fixture_harness.py loads the fixture."""
 
 from __future__ import annotations
-
-import json
-import os
 
 import numpy as np
 
 from oracle.graph_eval import INF, Node
-
-GOLDEN_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-CASES_PATH = os.path.join(GOLDEN_DIR, "playback_cases.json")
-NPZ_PATH = os.path.join(GOLDEN_DIR, "playback.npz")
+from oracle.spec_builder import is_spec
 
 NEW_KINDS = ("WavetablePE", "TimeWarpPE")
-
-
-def load_cases():
-    with open(CASES_PATH) as f:
-        cases = json.load(f)
-    return cases, np.load(NPZ_PATH)
-
-
-def stored_blocks(case):
-    """Indices of the blocks whose samples the fixture keeps (every `keep_every`-th; all by default)."""
-    k = int(case.get("keep_every", 1))
-    return [i for i in range(len(case["blocks"])) if i % k == 0]
-
-
-def split_blocks(case, flat):
-    """The fixture's concatenated samples -> {block index: samples} for the stored blocks."""
-    out, at = {}, 0
-    for i in stored_blocks(case):
-        n = int(case["blocks"][i][1])
-        out[i] = flat[at:at + n]
-        at += n
-    assert at == len(flat)
-    return out
-
-
-# ---------------------------------------------------------------------------------------------- graphs
-def is_spec(v):
-    return isinstance(v, dict) and "pe" in v
-
-
-def build_graph(spec, build_existing, make_new):
-    """SPEC -> PE instance, bottom-up.  build_existing(spec) builds a node of an existing kind whose PE-valued
-    parameters are already instances (both SPEC builders pass anything that is not a SPEC through as a keyword
-    value); make_new(kind, kwargs) constructs a WavetablePE / TimeWarpPE (interpolation / out_of_bounds still strings)."""
-    node = {}
-    for k, v in spec.items():
-        if is_spec(v):
-            node[k] = build_graph(v, build_existing, make_new)
-        elif k == "inputs":
-            assert not any(_mentions_new(s) for s in v), "a MixPE input may not hold a WavetablePE / TimeWarpPE"
-            node[k] = v
-        else:
-            node[k] = v
-    if spec["pe"] in NEW_KINDS:
-        return make_new(spec["pe"], {k: v for k, v in node.items() if k != "pe"})
-    return build_existing(node)
-
-
-def _mentions_new(spec):
-    if not is_spec(spec):
-        return False
-    return spec["pe"] in NEW_KINDS or any(
-        _mentions_new(v) or (k == "inputs" and any(_mentions_new(s) for s in v)) for k, v in spec.items())
-
-
-def make_with(WavetablePE, TimeWarpPE, InterpolationMode, OutOfBoundsMode):
-    def make_new(kind, kw):
-        kw = dict(kw)
-        if "interpolation" in kw:
-            kw["interpolation"] = InterpolationMode(kw["interpolation"])
-        if kind == "WavetablePE":
-            if "out_of_bounds" in kw:
-                kw["out_of_bounds"] = OutOfBoundsMode(kw["out_of_bounds"])
-            return WavetablePE(kw.pop("wavetable"), kw.pop("indexer"), **kw)
-        return TimeWarpPE(kw.pop("source"), **kw)
-    return make_new
 
 
 # ---------------------------------------------------------------------------------------------- interpolated_lookup

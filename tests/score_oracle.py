@@ -1,28 +1,12 @@
 """Shared by tools/gen_golden_score.py (over the reference's classes) and the score tests (over pygmu2_amd's): the
-fixture loader, the builder that turns a case of tests/golden/score_cases.json into a graph over a namespace of PE
+builder that turns a case of tests/golden/score_cases.json into a graph over a namespace of PE
 classes, the block patterns, and numpy restatements the tests check the bank's host tables and kernels against."""
 
 from __future__ import annotations
 
-import json
-import os
-
 import numpy as np
 
-GOLDEN_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-CASES_PATH = os.path.join(GOLDEN_DIR, "score_cases.json")
-NPZ_PATH = os.path.join(GOLDEN_DIR, "score.npz")
 SR = 8000
-
-# float paths (SinePE, BlitSawPE): the bar of tests/test_gpu_parity.py, which is where those sources are tested
-REL_TOL = 1e-5
-ABS_FLOOR = 1e-7
-
-
-def load_cases():
-    with open(CASES_PATH) as f:
-        data = json.load(f)
-    return data, np.load(NPZ_PATH)
 
 
 # ---------------------------------------------------------------------------------------------- graphs
@@ -85,14 +69,6 @@ def patterns(first: int, end: int):
         "seek_back": [[first, 1000], [first + 500, 1000], [first + 1500, 777], [first + 300, 256],
                       [first + 2277, max(1, span - 2277) + 50]],
     }
-
-
-def render_blocks(pe, renderer, blocks):
-    renderer.set_source(pe)
-    renderer.start()
-    outs = [np.array(pe.render(int(s), int(n)).data, dtype=np.float32) for s, n in blocks]
-    renderer.stop()
-    return outs
 
 
 def expected(case, pattern, npz):

@@ -1,28 +1,12 @@
 """KarplusStrongPE / AnalogOscPE restatements (re-exported from oracle/sources_oracle.py, where the graph oracle uses
-them too), the fixture loader, and the graph builder shared by the fixture generator (tools/gen_golden_sources.py, over
-the reference's classes) and the tests (over pygmu2_amd's)."""
+them too) and the builder of this family's graph format, shared by the fixture generator (tools/gen_golden_sources.py,
+over the reference's classes) and the tests (over pygmu2_amd's).  tests/fixture_harness.py loads the fixture."""
 
 from __future__ import annotations
 
-import json
-import os
-
-import numpy as np
-
 from oracle.sources_oracle import AnalogOsc, KarplusStrong, ks_geometry  # noqa: F401  (re-exported)
 
-GOLDEN_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-CASES_PATH = os.path.join(GOLDEN_DIR, "sources_cases.json")
-NPZ_PATH = os.path.join(GOLDEN_DIR, "sources.npz")
 
-
-def load_cases():
-    with open(CASES_PATH) as f:
-        cases = json.load(f)
-    return cases, np.load(NPZ_PATH)
-
-
-# ---------------------------------------------------------------------------------------------- graphs
 def build_graph(M, spec):
     """Instantiate a JSON graph spec over the namespace M (KarplusStrongPE, AnalogOscPE, SinePE, TransformPE,
     PiecewisePE, LadderPE, LadderMode, GainPE, CropPE, DelayPE, MixPE and affine(scale, offset) -> callable)."""
@@ -40,10 +24,4 @@ def build_graph(M, spec):
     if t == "LadderPE" and "mode" in kwargs:
         kwargs["mode"] = getattr(M.LadderMode, kwargs["mode"])
     return getattr(M, t)(*args, **kwargs)
-
-
-def stored_blocks(case):
-    """Indices of the blocks whose samples the fixture keeps (every `keep_every`-th; all by default)."""
-    k = int(case.get("keep_every", 1))
-    return [i for i in range(len(case["blocks"])) if i % k == 0]
 

@@ -9,33 +9,21 @@ import pytest
 import pygmu2_amd as pg
 import control_oracle as P
 import spec_build
+from fixture_harness import bits_equal, load_cases, split_blocks
 
-CASES, NPZ = P.load_cases()
+CASES, NPZ = load_cases("control")
 ALL = CASES["cases"]
 BY_NAME = {c["name"]: c for c in ALL}
 
 
-def bits_equal(a, b):
-    a, b = np.ascontiguousarray(a, np.float32), np.ascontiguousarray(b, np.float32)
-    return a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32))
-
-
 def build_pg(case):
-    pg.set_sample_rate(case["sr"])
-    made = []
-    make = P.make_with(pg.SampleHoldPE, pg.TrackHoldPE, pg.SlewLimiterPE, pg.SlewMode, pg.FunctionGenPE)
-
-    def make_new(kind, kw):
-        made.append(make(kind, kw))
-        return made[-1]
-
-    return P.build_graph(case["graph"], spec_build.build, make_new), made
+    return spec_build.build_case(case, P.NEW_KINDS)
 
 
 @pytest.mark.parametrize("case", ALL, ids=[c["name"] for c in ALL])
 def test_restatement_equals_fixture_bit_for_bit(case):
     outs, _ = P.run_case(case)
-    stored = P.split_blocks(case, NPZ[case["name"]])
+    stored = split_blocks(case, NPZ[case["name"]])
     assert stored
     for i, want in stored.items():
         assert bits_equal(outs[i], want), f"{case['name']}: block {i} differs"
@@ -74,7 +62,7 @@ def test_fixture_covers_what_it_must():
         assert iv != 0.0 and float(np.float32(iv)) != iv
         first = node.sub[control].render(*case["blocks"][0])[:, 0]
         assert not np.any(first > threshold)
-        assert np.all(P.split_blocks(case, NPZ[case["name"]])[0] == np.float32(iv))
+        assert np.all(split_blocks(case, NPZ[case["name"]])[0] == np.float32(iv))
         # a latch on the first and on the last sample of a block
         case = BY_NAME[f"{p}_latch_first_last"]
         node = _new_nodes(case, kind)[0]

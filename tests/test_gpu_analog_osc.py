@@ -6,13 +6,14 @@ import numpy as np
 import pytest
 
 import pygmu2_amd as pg
+from fixture_harness import load_cases
 from pygmu2_amd import look_ahead
 from sources_gpu_common import bits_equal, render_case, stream
-from sources_oracle import AnalogOsc, load_cases
+from sources_oracle import AnalogOsc
 
 pytestmark = pytest.mark.gpu
 
-DATA, NPZ = load_cases()
+DATA, NPZ = load_cases("sources")
 OSC_CASES = [c for c in DATA["cases"] if c["kind"] == "osc"]
 SR = 44100
 

@@ -5,7 +5,7 @@ and odd-sized blocks; look-ahead on against off with a seek and a reset_state() 
 noise -> sample-and-hold -> slew -> filter-cutoff patch.
 
 Holds, pure and exact-sum generators and rectangles are held to the bit.  SlewLimiterPE and the inexact-sum sawtooth
-are held to 1e-6 of the case's peak (PEAK_BOUND): their float64 entry levels / phase sums are re-associated."""
+are held to 1e-6 of the case's peak (fixture_harness.PEAK_BOUND): their float64 entry levels / phase sums are re-associated."""
 
 import os
 import subprocess
@@ -18,12 +18,13 @@ import pytest
 import pygmu2_amd as pg
 import control_oracle as P
 from control_gpu_common import assert_bits, assert_close, check_case
+from fixture_harness import load_cases
 from oracle.golden_cases import materialize_array
 from pygmu2_amd import look_ahead
 
 pytestmark = pytest.mark.gpu
 
-CASES, NPZ = P.load_cases()
+CASES, NPZ = load_cases("control")
 BY_NAME = {c["name"]: c for c in CASES["cases"]}
 FIXED = [c for c in CASES["cases"] if not c.get("fuzz")]
 SR = 48000

@@ -8,10 +8,11 @@ import pytest
 
 import control_oracle as P
 from control_gpu_common import check_case
+from fixture_harness import load_cases
 
 pytestmark = pytest.mark.gpu
 
-CASES, NPZ = P.load_cases()
+CASES, NPZ = load_cases("control")
 FUZZ = [c for c in CASES["cases"] if c.get("fuzz")]
 
 

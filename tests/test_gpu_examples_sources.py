@@ -9,12 +9,12 @@ constant shift (1e-5 of peak), the rectangle graphs by their audible shape (corr
 import numpy as np
 import pytest
 
+from fixture_harness import load_cases, stored_blocks
 from sources_gpu_common import bits_equal, render_case
-from sources_oracle import load_cases, stored_blocks
 
 pytestmark = pytest.mark.gpu
 
-DATA, NPZ = load_cases()
+DATA, NPZ = load_cases("sources")
 EXAMPLES = [c for c in DATA["cases"] if c["kind"] == "example"]
 FIRST_WRAP = {"ex21_pwm": 4410, "ex21_morph": 2205, "ex21_subtractive": 4410}
 

@@ -6,14 +6,15 @@ import numpy as np
 import pytest
 
 import pygmu2_amd as pg
+from fixture_harness import load_cases
 from pygmu2_amd import device, look_ahead
 from pygmu2_amd.device import DeviceBuffer
 from sources_gpu_common import bits_equal, render_case, stream
-from sources_oracle import KarplusStrong, ks_geometry, load_cases
+from sources_oracle import KarplusStrong, ks_geometry
 
 pytestmark = pytest.mark.gpu
 
-DATA, NPZ = load_cases()
+DATA, NPZ = load_cases("sources")
 KS_CASES = [c for c in DATA["cases"] if c["kind"] == "ks"]
 
 

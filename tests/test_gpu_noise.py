@@ -10,12 +10,13 @@ import pytest
 
 import pygmu2_amd as pg
 import noise_oracle as P
+from fixture_harness import load_cases
 from noise_gpu_common import assert_bits, check_case
 from pygmu2_amd import look_ahead
 
 pytestmark = pytest.mark.gpu
 
-CASES, NPZ = P.load_cases()
+CASES, NPZ = load_cases("noise")
 FIXED = [c for c in CASES["cases"] if not c.get("fuzz")]
 SR = 48000
 LONG = 1_000_000

@@ -6,11 +6,12 @@ so the exported-PE fuzz census (tests/test_oracle_fuzz_golden.py) does not reach
 import pytest
 
 import noise_oracle as P
+from fixture_harness import load_cases
 from noise_gpu_common import check_case
 
 pytestmark = pytest.mark.gpu
 
-CASES, NPZ = P.load_cases()
+CASES, NPZ = load_cases("noise")
 FUZZ = [c for c in CASES["cases"] if c.get("fuzz")]
 
 

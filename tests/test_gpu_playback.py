@@ -9,12 +9,13 @@ import pytest
 import pygmu2_amd as pg
 import playback_oracle as P
 from oracle.golden_cases import materialize_array
-from playback_gpu_common import PEAK_BOUND, bits_equal, build_case, check_case
+from fixture_harness import PEAK_BOUND, bits_equal, load_cases, split_blocks
+from playback_gpu_common import build_case, check_case
 from pygmu2_amd import diagnostics, timewarp_pe, wavetable_pe
 
 pytestmark = pytest.mark.gpu
 
-CASES, NPZ = P.load_cases()
+CASES, NPZ = load_cases("playback")
 BY_NAME = {c["name"]: c for c in CASES["cases"]}
 FIXED = [c for c in CASES["cases"] if not c.get("fuzz")]
 SR = 48000
@@ -68,7 +69,7 @@ def test_reset_and_restart_rewind_the_head(name):
     assert case["ops"] == {"2": "reset", "4": "restart"}
     check_case(case, NPZ)
     # the fixture shows the head back at 0: the blocks after each call repeat the first two
-    blocks = P.split_blocks(case, NPZ[name])
+    blocks = split_blocks(case, NPZ[name])
     assert bits_equal(blocks[2], blocks[0]) and bits_equal(blocks[4], blocks[0]) and bits_equal(blocks[5], blocks[1])
 
 
@@ -176,7 +177,7 @@ def test_example20_speed_ramp():
     r = started(pe)
     outs = [pe.render(int(s), int(c)).data.copy() for s, c in case["blocks"]]
     r.stop()
-    for i, want in P.split_blocks(case, NPZ[case["name"]]).items():
+    for i, want in split_blocks(case, NPZ[case["name"]]).items():
         assert bits_equal(outs[i], want), f"block {i}"
     assert float(np.max(np.abs(NPZ[case["name"]]))) > 0.5
 

@@ -4,12 +4,12 @@ graphs whose head positions are sums of a float64 rate that is not exact (1.1), 
 
 import pytest
 
-import playback_oracle as P
+from fixture_harness import load_cases
 from playback_gpu_common import check_case
 
 pytestmark = pytest.mark.gpu
 
-CASES, NPZ = P.load_cases()
+CASES, NPZ = load_cases("playback")
 FUZZ = [c for c in CASES["cases"] if c.get("fuzz")]
 
 

@@ -7,25 +7,21 @@ the bank off in the same process: equal, the bank adds no rounding of its own.  
 against numpy / against pgx_karplus_strong one string at a time, and a 300-note pluck score whole, in blocks and after
 reset_state against the float32 restatement of tests/sources_oracle.py."""
 
-import types
-
 import numpy as np
 import pytest
 
 import pygmu2_amd as pg
 from pygmu2_amd import device, score_bank
 from pygmu2_amd.device import DeviceBuffer
-from score_oracle import (ABS_FLOOR, REL_TOL, SR, build_case, expected, load_cases, ordered_sum, render_blocks)
-from sources_gpu_common import bits_equal
+from fixture_harness import REL_TOL, SCORE_ABS_FLOOR as ABS_FLOOR, bits_equal, load_cases, render_blocks
+from score_oracle import SR, build_case, expected, ordered_sum
+from spec_build import PG
 from sources_oracle import KarplusStrong, ks_geometry
 
 pytestmark = pytest.mark.gpu
 
-DATA, NPZ = load_cases()
+DATA, NPZ = load_cases("score")
 CASES = DATA["cases"]
-PG = types.SimpleNamespace(
-    KarplusStrongPE=pg.KarplusStrongPE, BlitSawPE=pg.BlitSawPE, SinePE=pg.SinePE, NoisePE=pg.NoisePE,
-    ArrayPE=pg.ArrayPE, CropPE=pg.CropPE, DelayPE=pg.DelayPE, MixPE=pg.MixPE, SequencePE=pg.SequencePE)
 _RENDERS = {}
 
 
@@ -41,7 +37,7 @@ def _render(case, pattern, bank):
         score_bank.set_enabled(bank)
         try:
             pe = build_case(PG, case)
-            outs = render_blocks(pe, pg.NullRenderer(sample_rate=SR), case["patterns"][pattern])
+            outs = render_blocks(pe, SR, case["patterns"][pattern])
             mix = _mix_of(pe)
             if isinstance(mix, pg.MixPE):
                 assert bool(mix._score) == bank, "the score bank was not what rendered this case"
@@ -244,7 +240,7 @@ def test_300_note_pluck_score_whole_blocks_and_reset():
                               for i in range(count)])
 
     pe = make()
-    whole = render_blocks(pe, pg.NullRenderer(sample_rate=SR), [[0, total]])[0]
+    whole = render_blocks(pe, SR, [[0, total]])[0]
     assert pe.inputs()[0]._score and np.array_equal(whole, want)
     pe = make()
     r = pg.NullRenderer(sample_rate=SR)

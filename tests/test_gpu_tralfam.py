@@ -12,11 +12,12 @@ import pytest
 
 import pygmu2_amd as pg
 import tralfam_oracle as T
-from tralfam_gpu_common import check_case, max_err
+from fixture_harness import PEAK_BOUND, load_cases, max_err
+from tralfam_gpu_common import check_case
 
 pytestmark = pytest.mark.gpu
 
-CASES, NPZ = T.load_cases()
+CASES, NPZ = load_cases("tralfam")
 ALL = CASES["cases"]
 
 
@@ -118,4 +119,4 @@ def test_device_matches_the_bluestein_model_through_the_pe():
     peak = float(np.max(np.abs(want)))
     err = max_err(got, want)
     print(f"TRALFAM_ERR model n={n} max_abs_err={err:.3e} peak={peak:.3e}")
-    assert err <= T.PEAK_BOUND * peak
+    assert err <= PEAK_BOUND * peak

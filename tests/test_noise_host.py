@@ -10,53 +10,32 @@ import numpy as np
 import pytest
 
 import pygmu2_amd as pg
-import control_oracle as C
 import noise_oracle as P
 import spec_build
+from fixture_harness import bits_equal, load_cases, split_blocks, within
 from pygmu2_amd import device
 from pygmu2_amd.build import build
 
-CASES, NPZ = P.load_cases()
+CASES, NPZ = load_cases("noise")
 ALL = CASES["cases"]
 BY_NAME = {c["name"]: c for c in ALL}
 SEEDS = (0, 1, 12345, 2 ** 63 + 5, 2 ** 100 + 7)
 OFFSETS = (0, 1, 2 ** 20 + 3, 2 ** 32 + 1, 2 ** 40)
 
 
-def bits_equal(a, b):
-    a, b = np.ascontiguousarray(a, np.float32), np.ascontiguousarray(b, np.float32)
-    return a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32))
-
-
 def build_pg(case):
-    pg.set_sample_rate(case["sr"])
-    made = []
-    make = P.make_with(pg.NoisePE, pg.NoiseMode,
-                       C.make_with(pg.SampleHoldPE, pg.TrackHoldPE, pg.SlewLimiterPE, pg.SlewMode, pg.FunctionGenPE))
-
-    def make_new(kind, kw):
-        pe = make(kind, kw)
-        if kind == P.KIND:
-            made.append(pe)
-        return pe
-
-    return P.build_graph(case["graph"], spec_build.build, make_new, lambda inputs: pg.MixPE(*inputs)), made
+    return spec_build.build_case(case, (P.KIND,))
 
 
 @pytest.mark.parametrize("case", ALL, ids=[c["name"] for c in ALL])
 def test_restatement_equals_fixture(case):
     outs, _ = P.run_case(case)
     flat = NPZ[case["name"]]
-    stored = P.split_blocks(case, flat)
+    stored = split_blocks(case, flat)
     assert stored
     peak = float(np.max(np.abs(flat)))
     for i, want in stored.items():
-        if case["compare"] == "bits":
-            assert bits_equal(outs[i], want), f"{case['name']}: block {i} differs"
-            continue
-        err = float(np.max(np.abs(outs[i].astype(np.float64) - want.astype(np.float64))))
-        bound = P.PEAK_BOUND * peak if case["compare"] == "peak" else P.REL_TOL * float(np.max(np.abs(want))) + P.ABS_FLOOR
-        assert outs[i].shape == want.shape and err <= bound, f"{case['name']}: block {i}: {err:.3g} > {bound:.3g}"
+        assert within(case["compare"], outs[i], want, peak), f"{case['name']}: block {i} differs ({case['compare']})"
 
 
 @pytest.mark.parametrize("seed", SEEDS)
@@ -137,7 +116,7 @@ def test_fixture_covers_what_it_must():
         assert np.all(NPZ[f"{mode}_range_point"] == np.float32(-0.3))
     # a reset and a restart go back to the seed: blocks 2 and 4 repeat block 0
     for mode in P.MODES:
-        blocks = P.split_blocks(BY_NAME[f"{mode}_reset_restart"], NPZ[f"{mode}_reset_restart"])
+        blocks = split_blocks(BY_NAME[f"{mode}_reset_restart"], NPZ[f"{mode}_reset_restart"])
         assert bits_equal(blocks[2], blocks[0]) and bits_equal(blocks[4], blocks[0]) and not bits_equal(blocks[1], blocks[0])
     rails = NPZ["brown_rails"][:, 0]
     assert rails[3941] == 1.0 and rails[7511] == -1.0 and np.max(np.abs(rails[:3941])) < 1.0

@@ -9,13 +9,12 @@ import pytest
 
 import pygmu2_amd as pg
 from pygmu2_amd import score_bank
-from score_oracle import SR, brute_active, brute_tile_lists, build_case, load_cases
+from fixture_harness import load_cases
+from score_oracle import SR, brute_active, brute_tile_lists, build_case
+from spec_build import PG
 
-DATA, _ = load_cases()
+DATA, _ = load_cases("score")
 CASES = DATA["cases"]
-PG = types.SimpleNamespace(
-    KarplusStrongPE=pg.KarplusStrongPE, BlitSawPE=pg.BlitSawPE, SinePE=pg.SinePE, NoisePE=pg.NoisePE,
-    ArrayPE=pg.ArrayPE, CropPE=pg.CropPE, DelayPE=pg.DelayPE, MixPE=pg.MixPE, SequencePE=pg.SequencePE)
 
 
 @pytest.fixture(autouse=True)

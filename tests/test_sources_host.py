@@ -8,11 +8,12 @@ import numpy as np
 import pytest
 
 import pygmu2_amd as pg
+from fixture_harness import load_cases, stored_blocks
 from pygmu2_amd import device, look_ahead, read_ahead
-from sources_oracle import AnalogOsc, KarplusStrong, load_cases, stored_blocks
+from sources_oracle import AnalogOsc, KarplusStrong
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DATA, NPZ = load_cases()
+DATA, NPZ = load_cases("sources")
 CASES = DATA["cases"]
 
 

@@ -9,25 +9,18 @@ import numpy as np
 import pytest
 
 import pygmu2_amd as pg
+import spec_build
 import tralfam_oracle as T
+from fixture_harness import ABS_FLOOR, PEAK_BOUND, REL_TOL, load_cases
 from pygmu2_amd import device
 from pygmu2_amd.build import build
 
-CASES, NPZ = T.load_cases()
+CASES, NPZ = load_cases("tralfam")
 ALL = CASES["cases"]
 BY_NAME = {c["name"]: c for c in ALL}
 OFFSETS = (0, 1, 2 ** 20 + 3, 2 ** 32 + 1, 2 ** 40)
 LENGTHS = (1, 2, 3, 7, 128, 1000, 4096, 65_536, 4097, 16_964, 105_164, 99_991, 132_300, 156_168, 1_048_577,
            2 ** 21 - 1, 2 ** 21)
-
-
-def pg_namespace():
-    import types
-    K = types.SimpleNamespace(ArrayPE=pg.ArrayPE, DelayPE=pg.DelayPE, LoopPE=pg.LoopPE, CropPE=pg.CropPE,
-                              NoisePE=pg.NoisePE, TralfamPE=pg.TralfamPE, SlicePE=pg.SlicePE,
-                              SetExtentPE=pg.SetExtentPE, ExtendMode=pg.ExtendMode)
-    K.wav = lambda name: pg.WavReaderPE(T.wav_path(name))
-    return K
 
 
 @pytest.fixture(scope="module")
@@ -64,9 +57,9 @@ def test_restatement_equals_fixture(case):
             assert float(np.max(np.abs(outs[0]))) == pytest.approx(peak, rel=1e-6)
         if peak == 0.0:
             assert not np.any(got), f"{case['name']}: a silent case must be exactly zero"
-        bound = T.PEAK_BOUND * peak
+        bound = PEAK_BOUND * peak
     else:
-        bound = T.REL_TOL * float(np.max(np.abs(want))) + T.ABS_FLOOR
+        bound = REL_TOL * float(np.max(np.abs(want))) + ABS_FLOOR
     assert err <= bound, f"{case['name']}: {err:.3g} > {bound:.3g}"
 
 
@@ -113,7 +106,7 @@ def test_chirp_phase_is_reduced_in_integers():
 @pytest.mark.parametrize("case", ALL, ids=[c["name"] for c in ALL])
 def test_host_side_equals_reference(case):
     pg.set_sample_rate(case["sr"])
-    _, pe, _ = T.build_case(case, pg_namespace(), NPZ)
+    _, pe, _ = T.build_case(case, spec_build.PG, NPZ)
     rec = case["pe"]
     want_repr = rec["repr"].replace("ArrayPE", "WavReaderPE") if case["source"]["kind"] == "wav" and \
         case["graph"] in ("plain", "slice", "set_extent") else rec["repr"]

@@ -1,5 +1,6 @@
-"""TralfamPE, SlicePE and SetExtentPE on the CPU, plus the fixture loader and the case plumbing shared by the fixture
-generator (tools/gen_golden_tralfam.py, over the reference's classes) and the tests (over pygmu2_amd's).
+"""TralfamPE, SlicePE and SetExtentPE on the CPU, plus the case plumbing shared by the fixture generator
+(tools/gen_golden_tralfam.py, over the reference's classes) and the tests (over pygmu2_amd's); tests/fixture_harness.py
+loads the fixture and holds the bounds.
 
 (a) The numpy restatement: `mogrify` is the reference's _mogrify (tralfam_pe.py:70-105) with every transform in float64,
     `Sig` / `restate_case` restate the graphs of the cases (finite signals with an extent; integer delay, crop, slice
@@ -16,32 +17,19 @@ sampled frames of one whole-extent render ("sampled": `sample_index`)."""
 
 from __future__ import annotations
 
-import json
 import os
 
 import numpy as np
 
 import noise_oracle as P
-
-GOLDEN_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-CASES_PATH = os.path.join(GOLDEN_DIR, "tralfam_cases.json")
-NPZ_PATH = os.path.join(GOLDEN_DIR, "tralfam.npz")
+from fixture_harness import GOLDEN_DIR
 
 F = np.float32
-PEAK_BOUND = 1e-6            # re-associated float64 sums rounded to float32 (control_oracle.PEAK_BOUND): x peak of the case
-REL_TOL = 1e-5               # tests/test_gpu_fuzz.py: a GainPE with a PE gain, per block REL_TOL * peak + ABS_FLOOR
-ABS_FLOOR = 1e-6
 DFT_FACTOR = 8.0             # pgx_dft_c2c: max |X_dev - X_numpy| <= DFT_FACTOR * 2^-52 * max(1, log2 M) * max |X_numpy|
 EPS = 2.0 ** -52
 SEEDS = (0, 1, 12345, 2 ** 63 + 5, 2 ** 100 + 7)
 FULL_STORE_LIMIT = 8192
 WINDOW = 1024
-
-
-def load_cases():
-    with open(CASES_PATH) as f:
-        cases = json.load(f)
-    return cases, np.load(NPZ_PATH)
 
 
 # ------------------------------------------------------------------------------------------------- (c) the inputs

@@ -23,30 +23,16 @@ import json
 import os
 import sys
 
-import numpy as np
-
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
-from oracle.gen_golden import build, has_kind, load_reference  # noqa: E402
-from oracle.gen_golden_fuzz import write_npz                    # noqa: E402
+from oracle.gen_golden import load_reference, render_case  # noqa: E402
+from oracle.gen_golden_fuzz import choose_keep, write_npz                    # noqa: E402
 
 BUDGET = 800          # stored samples (frames x channels) per case (a case may ask for its own), at least one block
 CASES_PATH = os.path.join(ROOT, "tests", "golden", "channels_cases.json")
 NPZ_PATH = os.path.join(ROOT, "tests", "golden", "channels.npz")
-
-
-def choose_keep(outs, budget=BUDGET):
-    """Blocks from the last backwards while they fit the budget; the smallest block if none does."""
-    keep, left = [], budget
-    for i in range(len(outs) - 1, -1, -1):
-        if outs[i].size <= left:
-            keep.append(i)
-            left -= outs[i].size
-    if not keep:
-        keep = [int(np.argmin([o.size for o in outs]))]
-    return sorted(keep)
 
 
 def main():
@@ -56,18 +42,7 @@ def main():
     arrays, stored = {}, []
     for case in channel_cases.cases():
         assert F.osc_edge_distance(case) > 1e-9, (case["name"], "a stateful oscillator on a waveform edge: redraw")
-        M["config"].set_sample_rate(case["sr"])
-        pe = build(case["graph"], M)
-        r = M["null_renderer"].NullRenderer(sample_rate=case["sr"])
-        r.set_source(pe)
-        # as oracle/gen_golden.py: a reference ConvolvePE cannot be start()ed
-        if not (has_kind(case["graph"], "ConvolvePE") or has_kind(case["graph"], "ReverbPE")):
-            r.start()
-        outs = []
-        for s, n in case["blocks"]:
-            data = pe.render(int(s), int(n)).data
-            assert data.dtype == np.float32 and data.shape[0] == n, (case["name"], data.dtype, data.shape)
-            outs.append(np.ascontiguousarray(data))
+        outs = render_case(case, M)
         case["keep"] = choose_keep(outs, case.get("budget", BUDGET))
         for i in case["keep"]:
             arrays[f"{case['name']}/{i}"] = outs[i]

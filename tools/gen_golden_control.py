@@ -23,8 +23,6 @@ Checked while generating, against the reference alone:
 
 from __future__ import annotations
 
-import importlib
-import json
 import os
 import sys
 
@@ -35,7 +33,9 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 from oracle import gen_golden                                     # noqa: E402
+from oracle.gen_golden import affine, describe, render_reference, sums_exact, write_fixture      # noqa: E402
 from oracle.golden_cases import S, blocks_contig                  # noqa: E402
+from fixture_harness import PEAK_BOUND, stored_blocks             # noqa: E402
 import control_oracle as P                                         # noqa: E402
 
 SR = 48000
@@ -59,10 +59,6 @@ def SL(source, rise, fall=None, mode="linear"):
 def FG(frequency=1.0, duty_cycle=0.5, phase=0.0, waveform="rectangle", channels=1):
     return S("FunctionGenPE", frequency=frequency, duty_cycle=duty_cycle, phase=phase, waveform=waveform,
              channels=channels)
-
-
-def affine(src, scale, offset):
-    return S("TransformPE", source=src, ops=[["affine", scale, offset]])
 
 
 def noise(seed, n=2048, ch=1):
@@ -258,19 +254,6 @@ def fuzz_cases(count=40, seed=31):
 
 
 # ---------------------------------------------------------------------------------------------- checks
-def sums_exact(values):
-    """True when every sum of any of these float64 values, in any order, is exact: all are multiples of 2^-q and the
-    sum of their magnitudes times 2^q stays below 2^52."""
-    values = np.asarray(values, dtype=np.float64)
-    if not np.all(np.isfinite(values)):
-        return False
-    for q in range(0, 41):
-        scaled = values * 2.0 ** q
-        if np.all(scaled == np.round(scaled)):
-            return float(np.sum(np.abs(scaled))) < 2.0 ** 52
-    return False
-
-
 def fg_verdict(node, name):
     """"exact" (phase sums exact: bits), "rectangle" (inexact, clear of every edge: bits), "sawtooth" (peak)."""
     if not node.sub or not node.log:
@@ -296,58 +279,30 @@ def fg_verdict(node, name):
     return "rectangle" if rect else "sawtooth"
 
 
-def build_reference(case, mods, new):
-    made = []
+def perturbed(slew_type):
+    """A way to pull one block for gen_golden.render_reference: in PERTURB_EVERY-frame parts, the carried value of every
+    SlewLimiterPE moved by +-PERTURB (relative) before each of them."""
+    sign = [1.0]
 
-    def make_new(kind, kw, _make=P.make_with(new["sample_hold_pe"].SampleHoldPE, new["track_hold_pe"].TrackHoldPE,
-                                             new["slew_limiter_pe"].SlewLimiterPE, new["slew_limiter_pe"].SlewMode,
-                                             new["function_gen_pe"].FunctionGenPE)):
-        pe = _make(kind, kw)
-        made.append(pe)
-        return pe
-
-    pe = P.build_graph(case["graph"], lambda node: gen_golden.build(node, mods), make_new)
-    r = mods["null_renderer"].NullRenderer(sample_rate=case["sr"])
-    r.set_source(pe)
-    return pe, r, made
-
-
-def render_reference(case, mods, new, perturb=False):
-    pe, r, made = build_reference(case, mods, new)
-    slews = [m for m in made if isinstance(m, new["slew_limiter_pe"].SlewLimiterPE)]
-    r.start()
-    ops = {int(k): v for k, v in case.get("ops", {}).items()}
-    outs, sign = [], 1.0
-    for i, (s, n) in enumerate(case["blocks"]):
-        if ops.get(i) == "restart":
-            r.stop()
-            r.start()
-        elif ops.get(i) == "reset":
-            for m in made:
-                m.reset_state()
-        if not perturb:
-            outs.append(pe.render(int(s), int(n)).data.astype(np.float32))
-            continue
+    def render(pe, made, s, n):
         parts = []
-        for at in range(0, int(n), PERTURB_EVERY):
-            for m in slews:
-                m._current *= 1.0 + sign * PERTURB
-            sign = -sign
-            parts.append(pe.render(int(s) + at, min(PERTURB_EVERY, int(n) - at)).data.astype(np.float32))
-        outs.append(np.concatenate(parts))
-    r.stop()
-    return outs, pe, made
+        for at in range(0, n, PERTURB_EVERY):
+            for m in made:
+                if isinstance(m, slew_type):
+                    m._current *= 1.0 + sign[0] * PERTURB
+            sign[0] = -sign[0]
+            parts.append(pe.render(s + at, min(PERTURB_EVERY, n - at)).data.astype(np.float32))
+        return np.concatenate(parts)
+    return render
 
 
 def main():
     mods = gen_golden.load_reference()
-    new = {name: importlib.import_module(f"pygmu2.{name}")
-           for name in ("sample_hold_pe", "track_hold_pe", "slew_limiter_pe", "function_gen_pe")}
     arrays, all_cases = {}, cases()
     worst_perturbed = 0.0
     for case in all_cases:
         mods["config"].set_sample_rate(case["sr"])
-        outs, pe, made = render_reference(case, mods, new)
+        outs, pe, made = render_reference(case, mods, P.NEW_KINDS)
         restated, root = P.run_case(case)
         for i, (a, b) in enumerate(zip(outs, restated)):
             assert a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32)), \
@@ -357,26 +312,21 @@ def main():
         case["compare"] = "peak" if (has_slew or "sawtooth" in verdicts) else "bits"
         peak = max(float(np.max(np.abs(o))) for o in outs)
         if has_slew:
-            again, _, _ = render_reference(case, mods, new, perturb=True)
+            again, _, _ = render_reference(case, mods, P.NEW_KINDS, render=perturbed(mods["K"].SlewLimiterPE))
             err = max(float(np.max(np.abs(a.astype(np.float64) - b.astype(np.float64)))) for a, b in zip(outs, again))
-            assert err <= P.PEAK_BOUND * peak, \
+            assert err <= PEAK_BOUND * peak, \
                 f"{case['name']}: a 1e-13 perturbation of the carried value moves the output by {err / peak:.3g} of peak"
             worst_perturbed = max(worst_perturbed, err / peak)
         if case["compare"] == "peak":
             assert peak > 0.0, f"{case['name']}: a silent case has no peak to compare against"
         ext = pe.extent()
         case["extent"] = [ext.start, ext.end]
-        case["new_pes"] = [{"repr": repr(m), "extent": [m.extent().start, m.extent().end], "pure": m.is_pure(),
-                            "channels": m.channel_count(), "inputs": [type(i).__name__ for i in m.inputs()]}
-                           for m in made]
-        keep = P.stored_blocks(case)
+        case["new_pes"] = [describe(m) for m in made]
+        keep = stored_blocks(case)
         arrays[case["name"]] = np.concatenate([outs[i] for i in keep])
         print(f"{case['name']}: {arrays[case['name']].shape} {case['compare']}", flush=True)
     print(f"worst output change under the 1e-13 perturbation: {worst_perturbed:.3g} of peak")
-    with open(P.CASES_PATH, "w") as fh:
-        json.dump({"cases": all_cases}, fh, indent=1)
-    np.savez_compressed(P.NPZ_PATH, **arrays)
-    print(P.NPZ_PATH, os.path.getsize(P.NPZ_PATH), "bytes;", P.CASES_PATH, os.path.getsize(P.CASES_PATH), "bytes")
+    write_fixture("control", {"cases": all_cases}, arrays)
 
 
 if __name__ == "__main__":

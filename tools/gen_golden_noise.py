@@ -12,7 +12,7 @@ graph (in construction order), the lifecycle calls between blocks ("ops": reset_
 of the renderer before block i) and, per case, how it is compared:
     "bits"  nothing above the NoisePE re-associates: NoisePE alone, under MixPE, CropPE, integer DelayPE, constant GainPE,
             the holds;
-    "peak"  a SlewLimiterPE in the graph: max abs error <= 1e-6 * peak of the case (control_oracle.PEAK_BOUND);
+    "peak"  a SlewLimiterPE in the graph: max abs error <= 1e-6 * peak of the case (fixture_harness.PEAK_BOUND);
     "fuzz"  a filter, an oscillator or an envelope in the graph: per block max abs error <= 1e-5 * peak + 1e-6
             (tests/test_gpu_fuzz.py).
 
@@ -26,8 +26,6 @@ exact -1.0.
 
 from __future__ import annotations
 
-import importlib
-import json
 import os
 import sys
 
@@ -38,8 +36,9 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 from oracle import gen_golden                                     # noqa: E402
+from oracle.gen_golden import affine, describe, render_reference, write_fixture      # noqa: E402
 from oracle.golden_cases import S, blocks_contig                  # noqa: E402
-import control_oracle as C                                         # noqa: E402
+from fixture_harness import stored_blocks, within                 # noqa: E402
 import noise_oracle as P                                           # noqa: E402
 
 SR = 48000
@@ -53,15 +52,11 @@ def N(seed, mode="white", lo=-1.0, hi=1.0):
     return S("NoisePE", seed=seed, mode=mode, min_value=lo, max_value=hi)
 
 
-def affine(src, scale, offset):
-    return S("TransformPE", source=src, ops=[["affine", scale, offset]])
-
-
 def compare_rule(graph):
     kinds = P.kinds_of(graph)
     if "SlewLimiterPE" in kinds:
         return "peak"
-    if kinds <= BITS_KINDS and not (P.mentions(graph, "GainPE") and _gain_is_pe(graph)):
+    if kinds <= BITS_KINDS and not _gain_is_pe(graph):
         return "bits"
     return "fuzz"
 
@@ -170,86 +165,31 @@ def fuzz_cases(count=30, seed=41):
     return out
 
 
-def build_reference(case, mods, new):
-    made = []
-    make_control = C.make_with(new["sample_hold_pe"].SampleHoldPE, new["track_hold_pe"].TrackHoldPE,
-                               new["slew_limiter_pe"].SlewLimiterPE, new["slew_limiter_pe"].SlewMode,
-                               new["function_gen_pe"].FunctionGenPE)
-    make = P.make_with(new["noise_pe"].NoisePE, new["noise_pe"].NoiseMode, make_control)
-
-    def make_new(kind, kw):
-        pe = make(kind, kw)
-        if kind == P.KIND:
-            made.append(pe)
-        return pe
-
-    pe = P.build_graph(case["graph"], lambda node: gen_golden.build(node, mods), make_new,
-                       lambda inputs: mods["mix_pe"].MixPE(*inputs))
-    r = mods["null_renderer"].NullRenderer(sample_rate=case["sr"])
-    r.set_source(pe)
-    return pe, r, made
-
-
-def render_reference(case, mods, new):
-    pe, r, made = build_reference(case, mods, new)
-    r.start()
-    ops = {int(k): v for k, v in case.get("ops", {}).items()}
-    outs = []
-    for i, (s, n) in enumerate(case["blocks"]):
-        if ops.get(i) == "restart":
-            r.stop()
-            r.start()
-        elif ops.get(i) == "reset":
-            for m in made:
-                m.reset_state()
-        outs.append(pe.render(int(s), int(n)).data.astype(np.float32))
-    r.stop()
-    return outs, pe, made
-
-
-def within(rule, a, b, peak):
-    if rule == "bits":
-        return a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32))
-    err = float(np.max(np.abs(a.astype(np.float64) - b.astype(np.float64))))
-    if rule == "peak":
-        return a.shape == b.shape and err <= P.PEAK_BOUND * peak
-    return a.shape == b.shape and err <= P.REL_TOL * float(np.max(np.abs(a))) + P.ABS_FLOOR
-
-
 def main():
     assert int(np.__version__.split(".")[0]) >= 2, \
         f"numpy {np.__version__}: the float32 arithmetic of PINK / BROWN needs numpy >= 2 (NEP 50)"
     mods = gen_golden.load_reference()
-    new = {name: importlib.import_module(f"pygmu2.{name}")
-           for name in ("noise_pe", "sample_hold_pe", "track_hold_pe", "slew_limiter_pe", "function_gen_pe")}
     arrays, all_cases = {}, cases()
     for case in all_cases:
         mods["config"].set_sample_rate(case["sr"])
-        outs, pe, made = render_reference(case, mods, new)
+        outs, pe, made = render_reference(case, mods, (P.KIND,))
         restated, _ = P.run_case(case)
         peak = max(float(np.max(np.abs(o))) for o in outs)
         for i, (a, b) in enumerate(zip(outs, restated)):
-            assert within(case["compare"], a, b, peak), \
+            assert within(case["compare"], b, a, peak), \
                 f"{case['name']}: the restatement differs from the reference in block {i}"
         if case["compare"] != "bits":
             assert peak > 0.0, f"{case['name']}: a silent case has no peak to compare against"
         ext = pe.extent()
         case["extent"] = [ext.start, ext.end]
-        case["new_pes"] = [{"repr": repr(m), "extent": [m.extent().start, m.extent().end], "pure": m.is_pure(),
-                            "channels": m.channel_count(), "inputs": [type(i).__name__ for i in m.inputs()],
-                            "min_value": m.min_value, "max_value": m.max_value, "mode": m.mode.value}
+        case["new_pes"] = [dict(describe(m), min_value=m.min_value, max_value=m.max_value, mode=m.mode.value)
                            for m in made]
-        keep = P.stored_blocks(case)
+        keep = stored_blocks(case)
         arrays[case["name"]] = np.concatenate([outs[i] for i in keep])
         print(f"{case['name']}: {arrays[case['name']].shape} {case['compare']}", flush=True)
     rails = arrays["brown_rails"]
     assert np.any(rails == np.float32(1.0)) and np.any(rails == np.float32(-1.0)), "brown_rails misses a rail"
-    with open(P.CASES_PATH, "w") as fh:
-        json.dump({"numpy": np.__version__, "cases": all_cases}, fh, indent=1)
-    np.savez_compressed(P.NPZ_PATH, **arrays)
-    total = sum(a.size for a in arrays.values())
-    print(P.NPZ_PATH, os.path.getsize(P.NPZ_PATH), "bytes,", total, "samples;", P.CASES_PATH,
-          os.path.getsize(P.CASES_PATH), "bytes")
+    write_fixture("noise", {"numpy": np.__version__, "cases": all_cases}, arrays)
 
 
 if __name__ == "__main__":

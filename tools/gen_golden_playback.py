@@ -17,8 +17,6 @@ a sample to 0, and no tolerance on the positions covers that).
 
 from __future__ import annotations
 
-import importlib
-import json
 import os
 import sys
 
@@ -29,7 +27,9 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 from oracle import gen_golden                                     # noqa: E402
+from oracle.gen_golden import affine, describe, render_reference, sums_exact, write_fixture      # noqa: E402
 from oracle.golden_cases import S, blocks_contig                  # noqa: E402
+from fixture_harness import reset_all, stored_blocks              # noqa: E402
 import playback_oracle as P                                        # noqa: E402
 
 SR = 48000
@@ -42,10 +42,6 @@ def WT(table, indexer, interpolation="linear", out_of_bounds="zero"):
 
 def TW(source, rate, interpolation="linear"):
     return S("TimeWarpPE", source=source, rate=rate, interpolation=interpolation)
-
-
-def affine(src, scale, offset):
-    return S("TransformPE", source=src, ops=[["affine", scale, offset]])
 
 
 def noise(seed, n, ch=1):
@@ -231,52 +227,13 @@ def fuzz_cases(count=40, seed=20):
     return out
 
 
-# ---------------------------------------------------------------------------------------------- checks
-def sums_exact(rates):
-    """True when every sum of any of these float64 rates, in any order, is exact: all are multiples of 2^-q and the
-    sum of their magnitudes times 2^q stays below 2^52."""
-    rates = np.asarray(rates, dtype=np.float64)
-    if not np.all(np.isfinite(rates)):
-        return False
-    for q in range(0, 41):
-        scaled = rates * 2.0 ** q
-        if np.all(scaled == np.round(scaled)):
-            return float(np.sum(np.abs(scaled))) < 2.0 ** 52
-    return False
-
-
 def main():
     mods = gen_golden.load_reference()
-    mods["timewarp_pe"] = importlib.import_module("pygmu2.timewarp_pe")
-    wt_mod, tw_mod = mods["wavetable_pe"], mods["timewarp_pe"]
     arrays, all_cases = {}, cases()
     for case in all_cases:
         mods["config"].set_sample_rate(case["sr"])
-        made = []
-
-        def make_new(kind, kw, _make=P.make_with(wt_mod.WavetablePE, tw_mod.TimeWarpPE, wt_mod.InterpolationMode,
-                                                 wt_mod.OutOfBoundsMode)):
-            pe = _make(kind, kw)
-            made.append(pe)
-            return pe
-
-        pe = P.build_graph(case["graph"], lambda node: gen_golden.build(node, mods), make_new)
-        r = mods["null_renderer"].NullRenderer(sample_rate=case["sr"])
-        r.set_source(pe)
-        r.start()
-        ops = {int(k): v for k, v in case.get("ops", {}).items()}
-        outs = []
-        for i, (s, n) in enumerate(case["blocks"]):
-            if ops.get(i) == "restart":
-                r.stop()
-                r.start()
-            elif ops.get(i) == "reset":
-                for m in made:
-                    if isinstance(m, tw_mod.TimeWarpPE):
-                        m.reset_state()
-            outs.append(pe.render(int(s), int(n)).data.astype(np.float32))
-        r.stop()
-
+        outs, pe, made = render_reference(case, mods, P.NEW_KINDS, reset=lambda made: reset_all(
+            m for m in made if isinstance(m, mods["K"].TimeWarpPE)))
         restated, root = P.run_case(case)
         for i, (a, b) in enumerate(zip(outs, restated)):
             assert a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32)), \
@@ -299,16 +256,11 @@ def main():
         # what the reference says about the graph's root and about every new PE in it, for the host-side tests
         ext = pe.extent()
         case["extent"] = [ext.start, ext.end]
-        case["new_pes"] = [{"repr": repr(m), "extent": [m.extent().start, m.extent().end], "pure": m.is_pure(),
-                            "channels": m.channel_count(), "inputs": [type(i).__name__ for i in m.inputs()]}
-                           for m in made]
-        keep = P.stored_blocks(case)
+        case["new_pes"] = [describe(m) for m in made]
+        keep = stored_blocks(case)
         arrays[case["name"]] = np.concatenate([outs[i] for i in keep])
         print(f"{case['name']}: {arrays[case['name']].shape} {case['compare']}", flush=True)
-    with open(P.CASES_PATH, "w") as fh:
-        json.dump({"cases": all_cases}, fh, indent=1)
-    np.savez_compressed(P.NPZ_PATH, **arrays)
-    print(P.NPZ_PATH, os.path.getsize(P.NPZ_PATH), "bytes;", P.CASES_PATH, os.path.getsize(P.CASES_PATH), "bytes")
+    write_fixture("playback", {"cases": all_cases}, arrays)
 
 
 if __name__ == "__main__":

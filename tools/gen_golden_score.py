@@ -20,11 +20,9 @@ on), and rendering such a score in 256- and 777-frame blocks equals one whole re
 
 from __future__ import annotations
 
-import importlib
 import json
 import os
 import sys
-import types
 
 import numpy as np
 
@@ -33,6 +31,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 from oracle import gen_golden                                     # noqa: E402
+from fixture_harness import render_blocks                         # noqa: E402
 import score_oracle as S                                           # noqa: E402
 
 SR = S.SR
@@ -149,12 +148,9 @@ def refusals(K):
 
 
 def describe(pe):
-    ext = pe.extent()
-    return {"repr": repr(pe), "extent": [ext.start, ext.end], "pure": bool(pe.is_pure()),
-            "channels": pe.channel_count(), "inputs": [type(i).__name__ for i in pe.inputs()],
-            "inner_inputs": [type(i).__name__ for i in pe.inputs()[0].inputs()],
-            "mode": pe.mode.value if hasattr(pe, "mode") else None,
-            "pairs": [[type(p).__name__, int(s)] for p, s in getattr(pe, "_pairs", [])]}
+    return dict(gen_golden.describe(pe), inner_inputs=[type(i).__name__ for i in pe.inputs()[0].inputs()],
+                mode=pe.mode.value if hasattr(pe, "mode") else None,
+                pairs=[[type(p).__name__, int(s)] for p, s in getattr(pe, "_pairs", [])])
 
 
 def conversions(conv):
@@ -179,12 +175,7 @@ def conversions(conv):
 
 def main():
     mods = gen_golden.load_reference()
-    new = {name: importlib.import_module(f"pygmu2.{name}") for name in ("sequence_pe", "noise_pe")}
-    K = types.SimpleNamespace(
-        KarplusStrongPE=mods["karplus_strong_pe"].KarplusStrongPE, BlitSawPE=mods["blit_saw_pe"].BlitSawPE,
-        SinePE=mods["sine_pe"].SinePE, NoisePE=new["noise_pe"].NoisePE, ArrayPE=mods["array_pe"].ArrayPE,
-        CropPE=mods["crop_pe"].CropPE, DelayPE=mods["delay_pe"].DelayPE, MixPE=mods["mix_pe"].MixPE,
-        SequencePE=new["sequence_pe"].SequencePE)
+    K = mods["K"]
     mods["config"].set_sample_rate(SR)
     renderer = lambda: mods["null_renderer"].NullRenderer(sample_rate=SR)   # noqa: E731
     arrays, all_cases = {}, cases()
@@ -198,7 +189,7 @@ def main():
         case["same_as_whole"] = {}
         outs = {}
         for name, blocks in case["patterns"].items():
-            outs[name] = np.concatenate(S.render_blocks(S.build_case(K, case), renderer(), blocks))
+            outs[name] = np.concatenate(render_blocks(S.build_case(K, case), SR, blocks, renderer=renderer()))
         arrays[f"{case['name']}/whole"] = outs["whole"]
         probe = dict(case, patterns=case["patterns"], same_as_whole={p: True for p in outs})
         for name in outs:
@@ -222,11 +213,8 @@ def main():
             errors[name] = {"type": type(exc).__name__, "text": str(exc)}
         else:
             raise AssertionError(f"{name}: the reference accepted it")
-    with open(S.CASES_PATH, "w") as fh:
-        json.dump({"numpy": np.__version__, "sr": SR, "cases": all_cases, "refused": errors,
-                   "conversions": conversions(mods["conversions"])}, fh, indent=1)
-    np.savez_compressed(S.NPZ_PATH, **arrays)
-    print(S.NPZ_PATH, os.path.getsize(S.NPZ_PATH), "bytes;", S.CASES_PATH, os.path.getsize(S.CASES_PATH), "bytes")
+    gen_golden.write_fixture("score", {"numpy": np.__version__, "sr": SR, "cases": all_cases, "refused": errors,
+                                       "conversions": conversions(mods["conversions"])}, arrays)
 
 
 class _Files(dict):
@@ -253,7 +241,7 @@ def check_sum_of_notes(K, case, pe, renderer, whole):
             length = min(length, max(0, pairs[k + 1][1] - start))
         if length <= 0:
             continue
-        alone = S.render_blocks(src, renderer(), [[ext.start, length]])[0]
+        alone = render_blocks(src, SR, [[ext.start, length]], renderer=renderer())[0]
         lo = start + ext.start - w0
         want[lo:lo + length] = want[lo:lo + length] + alone
     assert np.array_equal(want, whole), f"{case['name']}: not the ordered sum of its notes"

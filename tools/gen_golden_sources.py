@@ -10,11 +10,8 @@ of stateful AnalogOscPE cases ("<name>/freq", "<name>/duty"), and the rho_for_de
 
 from __future__ import annotations
 
-import importlib
-import json
 import os
 import sys
-import types
 
 import numpy as np
 
@@ -22,8 +19,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
-from oracle.gen_golden import load_reference          # noqa: E402
-from sources_oracle import CASES_PATH, NPZ_PATH, build_graph, stored_blocks   # noqa: E402
+from oracle.gen_golden import load_reference, write_fixture          # noqa: E402
+from fixture_harness import render_blocks, stored_blocks      # noqa: E402
+from sources_oracle import build_graph                        # noqa: E402
 
 
 def contig(start, sizes):
@@ -142,26 +140,17 @@ def main():
     global rho_for_decay_db_ref
     mods = load_reference()
     mods["config"].set_sample_rate(44100)
-    ks_mod = importlib.import_module("pygmu2.karplus_strong_pe")
-    osc_mod = importlib.import_module("pygmu2.analog_osc_pe")
+    ks_mod = mods["karplus_strong_pe"]
     rho_for_decay_db_ref = ks_mod.rho_for_decay_db
-    M = types.SimpleNamespace(
-        KarplusStrongPE=ks_mod.KarplusStrongPE, AnalogOscPE=osc_mod.AnalogOscPE,
-        SinePE=mods["sine_pe"].SinePE, TransformPE=mods["transform_pe"].TransformPE,
-        PiecewisePE=mods["piecewise_pe"].PiecewisePE, LadderPE=mods["ladder_pe"].LadderPE,
-        LadderMode=mods["ladder_pe"].LadderMode, GainPE=mods["gain_pe"].GainPE, CropPE=mods["crop_pe"].CropPE,
-        DelayPE=mods["delay_pe"].DelayPE, MixPE=mods["mix_pe"].MixPE,
-        affine=lambda scale, offset: (lambda x: offset + scale * x))
+    M = mods["K"]
+    M.affine = lambda scale, offset: (lambda x: offset + scale * x)
     arrays = {}
     all_cases = cases()
     for case in all_cases:
         mods["config"].set_sample_rate(case["sr"])
         pe = build_graph(M, case["graph"])
         r = mods["null_renderer"].NullRenderer(sample_rate=case["sr"])
-        r.set_source(pe)
-        r.start()
-        outs = [pe.render(int(s), int(n)).data.astype(np.float32) for s, n in case["blocks"]]
-        r.stop()
+        outs = render_blocks(pe, case["sr"], case["blocks"], renderer=r)
         keep = stored_blocks(case)
         arrays[case["name"]] = np.concatenate([outs[i] for i in keep])
         if case["kind"] == "osc" and case["graph"]["kwargs"] and not pe.is_pure():
@@ -184,10 +173,7 @@ def main():
         except ValueError as e:
             errors.append([seconds, f, sr, str(e)])
     arrays["rho/grid"] = np.array(grid, dtype=np.float64)
-    with open(CASES_PATH, "w") as fh:
-        json.dump({"cases": all_cases, "rho_errors": errors}, fh, indent=1)
-    np.savez_compressed(NPZ_PATH, **arrays)
-    print(NPZ_PATH, os.path.getsize(NPZ_PATH), "bytes")
+    write_fixture("sources", {"cases": all_cases, "rho_errors": errors}, arrays)
 
 
 if __name__ == "__main__":

@@ -16,17 +16,14 @@ tests/golden/kemar/H0e030a.wav, which the reference side is handed as an ArrayPE
 own WavReaderPE needs the absent soundfile).
 
 Checked while generating, against the reference alone: the float64 restatement (tests/tralfam_oracle.py) gives every
-TralfamPE case within PEAK_BOUND * peak of the case, every SetExtentPE case and every SlicePE case without fades bit
+TralfamPE case within fixture_harness.PEAK_BOUND * peak of the case, every SetExtentPE case and every SlicePE case without fades bit
 for bit, and SlicePE with fades within the GainPE class; a silent case is exactly zero.
 """
 
 from __future__ import annotations
 
-import importlib
-import json
 import os
 import sys
-import types
 
 import numpy as np
 
@@ -35,6 +32,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 from oracle import gen_golden                                     # noqa: E402
+from fixture_harness import within                                # noqa: E402
 import tralfam_oracle as T                                         # noqa: E402
 
 SR = 48000
@@ -165,46 +163,18 @@ def cases():
     return c
 
 
-def reference_namespace(mods, new):
-    K = types.SimpleNamespace(
-        ArrayPE=mods["array_pe"].ArrayPE, DelayPE=mods["delay_pe"].DelayPE, LoopPE=mods["loop_pe"].LoopPE,
-        CropPE=mods["crop_pe"].CropPE, NoisePE=new["noise_pe"].NoisePE, TralfamPE=new["tralfam_pe"].TralfamPE,
-        SlicePE=new["slice_pe"].SlicePE, SetExtentPE=new["set_extent_pe"].SetExtentPE,
-        ExtendMode=mods["extent"].ExtendMode)
-    K.wav = lambda name: K.ArrayPE(T.read_wav(name))
-    return K
-
-
-def describe(pe):
-    ext = pe.extent()
-    return {"repr": repr(pe), "extent": [ext.start, ext.end], "pure": bool(pe.is_pure()),
-            "channels": pe.channel_count(), "inputs": [type(i).__name__ for i in pe.inputs()]}
-
-
-def within(case, got, want, peak):
-    if got.shape != want.shape:
-        return False
-    if case["compare"] == "bits" or peak == 0.0:
-        return np.array_equal(got, want)
-    err = float(np.max(np.abs(got.astype(np.float64) - want.astype(np.float64))))
-    if case["compare"] == "peak":
-        return err <= T.PEAK_BOUND * peak
-    return err <= T.REL_TOL * float(np.max(np.abs(want))) + T.ABS_FLOOR
-
-
 def main():
     assert int(np.__version__.split(".")[0]) >= 2, f"numpy {np.__version__}: the fixtures need numpy >= 2 (NEP 50)"
     mods = gen_golden.load_reference()
-    new = {name: importlib.import_module(f"pygmu2.{name}")
-           for name in ("noise_pe", "tralfam_pe", "slice_pe", "set_extent_pe")}
-    K = reference_namespace(mods, new)
+    K = mods["K"]
+    K.wav = lambda name: K.ArrayPE(T.read_wav(name))      # the reference's own WavReaderPE needs the absent soundfile
     arrays = short_inputs()
     all_cases = cases()
     worst = 0.0
     for case in all_cases:
         mods["config"].set_sample_rate(case["sr"])
         outs, pe = T.render_case(case, K, arrays)
-        case["pe"] = describe(pe)
+        case["pe"] = gen_golden.describe(pe)
         if case["compare"] == "peak":
             whole_out = np.concatenate(outs[:len(case["blocks"])])
             peak = float(np.max(np.abs(whole_out))) if whole_out.size else 0.0
@@ -216,7 +186,7 @@ def main():
         restated = T.restate_case(case, arrays)
         assert len(restated) == len(outs), case["name"]
         for i, (a, b) in enumerate(zip(outs, restated)):
-            assert within(case, b, a, peak), f"{case['name']}: the restatement differs from the reference in block {i}"
+            assert within(case["compare"], b, a, peak, silent="zero"), f"{case['name']}: the restatement differs from the reference in block {i}"
             if case["compare"] == "peak" and peak > 0 and a.size:
                 worst = max(worst, float(np.max(np.abs(a.astype(np.float64) - b.astype(np.float64)))) / peak)
         if case["source"]["kind"] == "silence":
@@ -224,10 +194,7 @@ def main():
         arrays[case["name"]] = T.stored_of(case, outs)
         print(f"{case['name']}: {arrays[case['name']].shape} {case['compare']} {case['store']}", flush=True)
     print(f"largest distance reference <-> float64 restatement: {worst:.3e} x peak")
-    with open(T.CASES_PATH, "w") as fh:
-        json.dump({"numpy": np.__version__, "cases": all_cases}, fh, indent=1)
-    np.savez_compressed(T.NPZ_PATH, **arrays)
-    print(T.NPZ_PATH, os.path.getsize(T.NPZ_PATH), "bytes;", T.CASES_PATH, os.path.getsize(T.CASES_PATH), "bytes")
+    gen_golden.write_fixture("tralfam", {"numpy": np.__version__, "cases": all_cases}, arrays)
 
 
 if __name__ == "__main__":
