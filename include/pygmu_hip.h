@@ -280,6 +280,41 @@ typedef struct {
 } pgx_transform_op;
 int pgx_transform(float *out, const float *in, int64_t n_elems, const pgx_transform_op *ops, int nops);
 
+/* TransformPE chains that hold a tuning step (pygmu2_amd/transforms.py: PitchToFreq, FreqToPitch, SemitonesToRatio,
+ * RatioToSemitones over temperament.py's EqualTemperament / JustIntonation): float32 -> float64 -> ops in order ->
+ * float32, one launch and one rounding for the whole chain.
+ * code 0-6: as pgx_transform, the same arithmetic.  Codes 7-10 read record tunings[op.tuning]:
+ *    7  equal, pitch -> freq   reference_freq * 2^((x - reference_pitch) / divisions)
+ *    8  equal, freq -> pitch   reference_pitch + divisions * log2(max(x, 1e-10) / reference_freq)
+ *    9  just,  pitch -> freq   temperament.py JustIntonation.pitch_to_freq: octave / scale-degree split, linear
+ *                              interpolation of the log2 table, exp2, * 2^octave, * reference_freq
+ *   10  just,  freq -> pitch   JustIntonation.freq_to_pitch: the nearest table entry (first minimum) in the octave
+ * (interval <-> ratio are the same codes with reference_pitch 0 and reference_freq 1.)
+ * A just record (num_notes = N >= 2) owns 2N + 1 doubles of `tables` from table_offset: log2(ratios[0..N-1]),
+ * log2(ratios[0] * 2.0) -- the upper neighbour of the last entry, across the octave -- and ratios[0..N-1];
+ * reference_pitch is the pitch of ratios[0] and reference_freq its frequency.  An equal record has num_notes 0. */
+typedef struct {
+    int32_t code;
+    int32_t tuning;                 /* codes 7-10: index into `tunings` */
+    double p0;
+    double p1;
+} pgx_tuning_op;
+typedef struct {
+    double reference_pitch;
+    double reference_freq;
+    double divisions;               /* equal: divisions per octave; just: (double)num_notes */
+    int64_t table_offset;
+    int32_t num_notes;
+    int32_t pad;
+} pgx_tuning_record;
+/* ops, tunings and tables are device memory that the caller built together (transform_pe.py): op.tuning and
+ * table_offset + 2 * num_notes are trusted as the other parameter blocks of this header are; the kernel only reads them. */
+int pgx_tuning(float *out, const float *in, int64_t n_elems, const pgx_tuning_op *ops, int nops,
+               const pgx_tuning_record *tunings, const double *tables);
+/* the same device functions float64 in, float64 out: one op (code 7-10) over one record, for the accuracy test */
+int pgx_selftest_tuning(double *out, const double *in, int64_t n, int code, const pgx_tuning_record *tunings,
+                        const double *tables);
+
 /* ------------------------------------------------------------------ DelayPE / PiecewisePE / WAV formats
  * (the callers and data formats either side of the path)
  * DelayPE's float / PE delay: interpolated_lookup (interpolated_lookup.py:28-130) over the rendered

@@ -87,6 +87,12 @@ from .sequence_pe import SequenceMode, SequencePE
 from .conversions import (freq_to_pitch, pitch_to_freq, ratio_to_semitones, samples_to_seconds, seconds_to_samples,
                           semitones_to_ratio)
 from . import score_bank
+# The temperaments and the global tuning: the same arrangement (pg.JustIntonation, pg.set_temperament ... work, none is
+# in __all__); tests/test_tuning_host.py and tests/test_gpu_tuning.py hold them to fixtures of the reference.
+from . import temperament
+from .temperament import (CustomTemperament, EqualTemperament, JustIntonation, PythagoreanTuning, Temperament,
+                          get_reference_frequency, get_temperament, set_baroque_pitch, set_concert_pitch,
+                          set_reference_frequency, set_temperament, set_verdi_tuning)
 from .utils import render_to_file
 from . import device, diagnostics
 

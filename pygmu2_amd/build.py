@@ -36,6 +36,7 @@ SOURCES = [
     "pgx_noise.hip",
     "pgx_spectral.hip",
     "pgx_score.hip",
+    "pgx_tuning.hip",
 ]
 
 # -ffp-contract=off: the parity contract is "same float64 operation order as the reference's

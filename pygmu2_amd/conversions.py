@@ -1,54 +1,62 @@
 """
 Unit conversions of the reference's conversions.py (:21-109, :168-281): pitch number <-> frequency, semitones <->
-frequency ratio, samples <-> seconds.  Host math in float64 on array-likes, the reference's expressions in its order,
-for its default tuning only: 12-tone equal temperament, A4 = pitch 69 = 440 Hz (temperament.py:137-167).  The
-temperament classes are not part of this package: any `temperament=` other than None raises NotImplementedError.
-ratio_to_db / db_to_ratio live in dynamics_pe.py.
+frequency ratio, samples <-> seconds.  Host math in float64 on array-likes, the reference's expressions in its order.
+
+The four tuning conversions take a `temperament=` (an instance of temperament.Temperament: EqualTemperament,
+JustIntonation, PythagoreanTuning, CustomTemperament or a subclass of the user's) and pitch_to_freq / freq_to_pitch a
+`reference_pitch=` / `reference_freq=`; whatever is None is read from the globals of temperament.py when the function is
+called (set_temperament, set_reference_frequency: 12-tone equal temperament, A4 = pitch 69 = 440 Hz until changed).
+Anything else passed as `temperament=` raises NotImplementedError.  TransformPE runs these four on the device
+(transforms.PitchToFreq ...).  ratio_to_db / db_to_ratio live in dynamics_pe.py.
 """
 
 from __future__ import annotations
 
 import numpy as np
 
-_DIVISIONS = 12
-_REFERENCE_PITCH = 69.0
-_REFERENCE_FREQ = 440.0
-_FLOOR = 1e-10                     # the reference's guard in front of log2
+from . import temperament as _tm
 
 
-def _default_tuning_only(temperament) -> None:
-    if temperament is not None:
+def _resolve(temperament) -> _tm.Temperament:
+    if temperament is None:
+        return _tm.get_temperament()
+    if not isinstance(temperament, _tm.Temperament):
         raise NotImplementedError(
-            "pygmu2_amd has no temperament module: only the default tuning (12-tone equal temperament, "
-            "A4 = 69 = 440 Hz) is available; pass temperament=None")
+            f"temperament= takes an instance of pygmu2_amd.temperament.Temperament (EqualTemperament, JustIntonation, "
+            f"PythagoreanTuning, CustomTemperament) or None for the global one, not {type(temperament).__name__}")
+    return temperament
 
 
-def pitch_to_freq(pitch, temperament=None):
-    """Frequency in Hz of a (possibly fractional) MIDI pitch number."""
-    _default_tuning_only(temperament)
-    pitch = np.asarray(pitch, dtype=np.float64)
-    return _REFERENCE_FREQ * (2.0 ** ((pitch - _REFERENCE_PITCH) / _DIVISIONS))
+def _reference(reference_pitch, reference_freq) -> tuple[float, float]:
+    if reference_freq is None or reference_pitch is None:
+        global_freq, global_pitch = _tm.get_reference_frequency()
+        reference_freq = global_freq if reference_freq is None else reference_freq
+        reference_pitch = global_pitch if reference_pitch is None else reference_pitch
+    return reference_pitch, reference_freq
 
 
-def freq_to_pitch(freq, temperament=None):
-    """MIDI pitch number of a frequency in Hz."""
-    _default_tuning_only(temperament)
-    freq = np.maximum(np.asarray(freq, dtype=np.float64), _FLOOR)
-    return _REFERENCE_PITCH + _DIVISIONS * np.log2(freq / _REFERENCE_FREQ)
+def pitch_to_freq(pitch, temperament=None, reference_pitch=None, reference_freq=None):
+    """Frequency in Hz of a (possibly fractional) pitch number."""
+    temp = _resolve(temperament)
+    reference_pitch, reference_freq = _reference(reference_pitch, reference_freq)
+    return temp.pitch_to_freq(pitch, reference_pitch, reference_freq)
+
+
+def freq_to_pitch(freq, temperament=None, reference_pitch=None, reference_freq=None):
+    """Pitch number of a frequency in Hz."""
+    temp = _resolve(temperament)
+    reference_pitch, reference_freq = _reference(reference_pitch, reference_freq)
+    return temp.freq_to_pitch(freq, reference_pitch, reference_freq)
 
 
 def semitones_to_ratio(semitones, temperament=None):
-    """Frequency ratio of an interval in semitones (12 -> 2.0)."""
-    _default_tuning_only(temperament)
-    semitones = np.asarray(semitones, dtype=np.float64)
-    return 2.0 ** (semitones / _DIVISIONS)
+    """Frequency ratio of an interval in scale degrees of the temperament (12-ET: 12 -> 2.0)."""
+    return _resolve(temperament).interval_to_ratio(semitones)
 
 
 def ratio_to_semitones(ratio, temperament=None):
-    """Interval in semitones of a frequency ratio (2.0 -> 12)."""
-    _default_tuning_only(temperament)
-    ratio = np.maximum(np.asarray(ratio, dtype=np.float64), _FLOOR)
-    return _DIVISIONS * np.log2(ratio)
+    """Interval in scale degrees of the temperament of a frequency ratio (12-ET: 2.0 -> 12)."""
+    return _resolve(temperament).ratio_to_interval(ratio)
 
 
 def samples_to_seconds(samples, sample_rate):

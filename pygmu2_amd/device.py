@@ -127,6 +127,8 @@ _SIGNATURES = [
     ("pgx_envelope_scratch_bytes", _Z, [_L, _I]),
     ("pgx_envelope", _I, [_P, _P, _L, _I, _D, _D, _I, _I, _L, _P, _P]),
     ("pgx_transform", _I, [_P, _P, _L, _P, _I]),
+    ("pgx_tuning", _I, [_P, _P, _L, _P, _I, _P, _P]),
+    ("pgx_selftest_tuning", _I, [_P, _P, _L, _I, _P, _P]),
     ("pgx_blitsaw", _I, [_P, _L, _I, _L, _I, _D, _P, _P, _L, _P, _L, _P, _L, _P, _P, _P]),
     ("pgx_blitsaw_workspace_bytes", _Z, [_I, _L, _I]),
     ("pgx_supersaw_sum", _I, [_P, _L, _I, _I, _L, _I, _P, _P, _P, _L]),
@@ -210,6 +212,9 @@ LADDER_PARAMS = np.dtype([("freq", "<f8"), ("resonance", "<f8"), ("drive", "<f8"
                           ("passband_gain", "<f8"), ("oversample", "<i4"), ("mode", "<i4")])
 COMB_PARAMS = np.dtype([("feedback", "<f8"), ("delay", "<i4"), ("buffer_len", "<i4")])
 TRANSFORM_OP = np.dtype([("code", "<i4"), ("pad", "<i4"), ("p0", "<f8"), ("p1", "<f8")])
+TUNING_OP = np.dtype([("code", "<i4"), ("tuning", "<i4"), ("p0", "<f8"), ("p1", "<f8")])
+TUNING_RECORD = np.dtype([("reference_pitch", "<f8"), ("reference_freq", "<f8"), ("divisions", "<f8"),
+                          ("table_offset", "<i8"), ("num_notes", "<i4"), ("pad", "<i4")])
 GATE_PARAMS = np.dtype([("dt", "<f8"), ("phase", "<f8"), ("duty", "<f8")])
 KS_PARAMS = np.dtype([("line_offset", "<i8"), ("n", "<i4"), ("two_phase", "<i4"), ("switch_at", "<i8"),
                       ("rho", "<f4"), ("rho_damping", "<f4"), ("c", "<f4"), ("pad", "<f4")])

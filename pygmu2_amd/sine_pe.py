@@ -30,9 +30,10 @@ class SinePE(ProcessingElement):
         return self.is_pure() or (not isinstance(self._phase, ProcessingElement) and float(self._phase) == 0.0)
 
     def __init__(self, frequency=440.0, amplitude=1.0, phase=0.0, channels: int = 1):
-        self._frequency = frequency
-        self._amplitude = amplitude
-        self._phase = phase
+        # a size-1 array is a scalar (JustIntonation's pitch_to_freq(60) has shape (1,)): float() of it is deprecated
+        self._frequency, self._amplitude, self._phase = (
+            float(p.reshape(-1)[0]) if isinstance(p, np.ndarray) and p.size == 1 else p
+            for p in (frequency, amplitude, phase))
         self._channels = channels
         self._params: DeviceBuffer | None = None      # uploaded once, lazily
         self._state: DeviceBuffer | None = None       # {accumulated_phase, initialised}
