@@ -933,6 +933,37 @@ typedef struct {
 int pgx_score_mix(float *out, int64_t frames, int channels, const pgx_score_seg *segs, int64_t n_segs,
                   const int32_t *tile_offsets, const int32_t *tile_list, int64_t tile_frames);
 
+/* ------------------------------------------------------------------ restart bank (pgx_restart.hip)
+ * TriggerRestartPE._render (trigger_restart_pe.py:72-98) and RandomSelectPE (random_select_pe.py:79-95) over sources
+ * whose samples depend on the frame index alone: a scan of the trigger block plus a gather from "takes" -- stretches of
+ * the sources rendered once -- instead of one render and one copy per event.  An event is a trigger sample > 0 (NaN
+ * and negative samples are none, +2 is one); only channel 0 of the trigger is read (trigger_stride floats per frame).
+ * The block is cut into tiles of PGX_RESTART_TILE frames and at most PGX_RESTART_MAX_SEGMENTS segments of whole tiles,
+ * one workgroup each; all arithmetic on indices is integer, so no result depends on that cut.
+ *
+ * pgx_restart_plan: summary_dev[0..4) = {events, index of the first (n: none), index of the last (-1: none), frames of
+ * the longest stretch [event, next event or n) (0: none)}.  workspace: PGX_RESTART_WORKSPACE_INT64 int64 of device
+ * scratch; it keeps the segments' partial results for pgx_restart_gather over the same trigger block.
+ *
+ * pgx_restart_gather: for frame t, ordinal = events at positions <= t and local = t - the last of them (ordinal 0:
+ * local = carry_local + t, the local time of frame 0 on the clock that runs in from earlier blocks; carry_local < 0:
+ * nothing has ever started).  slot = sel_dev[ordinal]; sel_dev has n_sel entries, entry 0 names the take of the
+ * running stretch, entry k that of the block's k-th event.  out[t, c] = takes[slot].ptr[(local - first) * channels + c]
+ * where first <= local < first + len, else 0; also 0 for a slot outside [0, n_takes), an ordinal outside [0, n_sel)
+ * and for ordinal 0 with carry_local < 0.  local is 64-bit throughout.  Nothing but `out` is written. */
+#define PGX_RESTART_TILE 2048
+#define PGX_RESTART_MAX_SEGMENTS 1024
+#define PGX_RESTART_WORKSPACE_INT64 (4 * PGX_RESTART_MAX_SEGMENTS)
+typedef struct {
+    const float *ptr;      /* len frames of `channels` interleaved floats: the source at local times first .. */
+    int64_t first;
+    int64_t len;
+} pgx_restart_take;
+int pgx_restart_plan(int64_t *summary_dev, void *workspace, const float *trigger, int trigger_stride, int64_t n);
+int pgx_restart_gather(float *out, int64_t n, int channels, const float *trigger, int trigger_stride,
+                       const void *workspace, int64_t carry_local, const int32_t *sel_dev, int64_t n_sel,
+                       const pgx_restart_take *takes_dev, int n_takes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -37,6 +37,7 @@ SOURCES = [
     "pgx_spectral.hip",
     "pgx_score.hip",
     "pgx_tuning.hip",
+    "pgx_restart.hip",
 ]
 
 # -ffp-contract=off: the parity contract is "same float64 operation order as the reference's

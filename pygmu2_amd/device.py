@@ -193,6 +193,8 @@ _SIGNATURES = [
     ("pgx_tralfam_workspace_bytes", _Z, [_L, _I]),
     ("pgx_tralfam", _I, [_P, _P, _L, _I, _P, _D, _P, _P]),
     ("pgx_score_mix", _I, [_P, _L, _I, _P, _L, _P, _P, _L]),
+    ("pgx_restart_plan", _I, [_P, _P, _P, _I, _L]),
+    ("pgx_restart_gather", _I, [_P, _L, _I, _P, _I, _P, _L, _P, _L, _P, _I]),
 ]
 
 EXPORTED_SYMBOLS = [s[0] for s in _SIGNATURES]
@@ -223,6 +225,10 @@ KS_NOTE = np.dtype([("params", "<u8"), ("line", "<u8"), ("state", "<u8"), ("star
                     ("dst", "<i8")])
 SCORE_INLINE = 16          # PGX_SCORE_INLINE: tables of at most this many entries travel in the kernel arguments
 SCORE_SEG = np.dtype([("data", "<u8"), ("first", "<i8"), ("frames", "<i8")])
+RESTART_TILE = 2048                 # PGX_RESTART_TILE: frames per tile of pgx_restart_plan / pgx_restart_gather
+RESTART_MAX_SEGMENTS = 1024         # PGX_RESTART_MAX_SEGMENTS: workgroups per launch at most
+RESTART_WORKSPACE_INT64 = 4 * RESTART_MAX_SEGMENTS
+RESTART_TAKE = np.dtype([("ptr", "<u8"), ("first", "<i8"), ("len", "<i8")])
 NOISE_PARAMS = np.dtype([("state_hi", "<u8"), ("state_lo", "<u8"), ("inc_hi", "<u8"), ("inc_lo", "<u8"),
                          ("consumed", "<i8"), ("scaled", "<i4"), ("span", "<f4"), ("min_value", "<f4"), ("pad", "<i4")])
 NOISE_STATE = np.dtype([("pink", "<f4", (7,)), ("brown", "<f4")])

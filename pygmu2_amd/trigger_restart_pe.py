@@ -3,12 +3,18 @@ TriggerRestartPE: restart a source at local time 0 on every trigger event
 (trigger_restart_pe.py:13-98).  Pure control flow: the trigger block is read back to find
 the event positions (4 bytes per frame), each stretch between events is one render of the
 source placed into the output with a device-to-device copy.
+
+A source whose samples depend on the frame index alone (restart_bank.eligible) takes the restart
+bank instead -- a bank of one candidate and no draws: the trigger is scanned on the device, the
+source is rendered once over the block's longest stretch and one launch gathers the block.  The
+samples are the same; restart_bank.set_enabled(False) restores the path above for every source.
 """
 
 from __future__ import annotations
 
 import numpy as np
 
+from . import restart_bank as _bank
 from ._kernels import check, lib, new_output
 from .extent import Extent
 from .processing_element import ProcessingElement
@@ -26,6 +32,7 @@ class TriggerRestartPE(ProcessingElement):
         self._trigger = trigger
         self._src = src
         self._origin: int | None = None          # absolute frame of the latest restart; None = none yet
+        self._bank = None                        # restart_bank.RestartBank; False: looked, the source may not enter
 
     def inputs(self) -> list[ProcessingElement]:
         return [self._trigger, self._src]
@@ -47,9 +54,29 @@ class TriggerRestartPE(ProcessingElement):
     def _forget_origin(self) -> None:
         self._origin = None
 
-    _reset_state = _on_start = _on_stop = _forget_origin
+    def _forget_all(self) -> None:
+        self._origin = None
+        if self._bank:
+            self._bank.forget()
+
+    _reset_state = _forget_origin
+    _on_start = _on_stop = _forget_all
+
+    def _gather_bank(self):
+        if not _bank.enabled():
+            return None
+        if self._bank is None:
+            self._bank = _bank.try_build(self._trigger, [self._src], self.channel_count() or 1) or False
+        return self._bank or None
 
     def _render(self, start: int, duration: int) -> Snippet:
+        bank = self._gather_bank()
+        if bank is not None:
+            bank.origin = self._origin           # the origin lives here: the two paths can be switched between blocks
+            out = bank.render(start, duration, 0, lambda count: [0] * count)
+            if out is not None:
+                self._origin = bank.origin
+                return out
         channels = self.channel_count() or 1
         out = new_output(duration, channels, zero=True)
         fired = np.flatnonzero(self._trigger.render(start, duration).data[:, 0] > 0)
