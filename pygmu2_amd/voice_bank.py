@@ -19,7 +19,9 @@ falls back to per-input rendering.
 
 from __future__ import annotations
 
+import functools
 import os
+from typing import NamedTuple
 
 import numpy as np
 
@@ -59,7 +61,6 @@ SEGMENTED_CHAIN_MAX = int(os.environ.get("PGX_BBW_MAX_BATCH", "256"))
 SEGMENTED_CHAIN = True       # ... and smaller banks (4 .. 256 voices: a rank's share of C5) as one launch in concurrent time
                              # segments (pgx_blitsaw_biquad_wide_seg: closed-form oscillator carries, the filters warm up)
 PIPELINE_FULL_SUPERSAW_BANK = True    # ... and for a bank that fills the chip (512 instances: the 17 us mix beside the next block's bank)
-PIPELINE_SUPERSAW_BANK = False  # the same overlap for the voices-summed-on-chip bank: measured slower (render_mix)
 VOICE_TILES = os.environ.get("PGX_VOICE_TILES", "1") != "0"   # BlitSaw -> Biquad [-> x envelope] voices mixed on chip (pgx_voice_tiles)
 VOICE_TILES_MIN_FRAMES = 4096
 VOICE_TILES_MAX_WARM = 2048  # pgx_voice_tiles_max_warm(): a filter has to settle (every entry of A^warm below 2^-90) within this many frames
@@ -71,7 +72,6 @@ VOICE_TILES_MIN_VOICES = int(os.environ.get("PGX_VOICE_TILES_MIN_VOICES", "16"))
                              # smaller banks -- 64 voices 56 us per block against 52.  In windows: 8 voices 33 against 45, 64 voices 40
                              # against 49, 128: 48 against 56, 256: 63 against 72, 512: 83 against 106.  Smaller banks keep the kernels
                              # that are bit-identical to the per-voice path)
-FUSE_GAIN_IN_CHAIN = False   # ... and multiplied into the voices by the oscillator -> filter kernel: measured, no gain (render_mix)
 EARLY_WALK_MAX_VOICES = int(os.environ.get("PGX_EARLY_WALK_MAX", "256"))  # ... started at once (not behind the block's oscillators) for banks up to this size
 ENVELOPE_AHEAD = True        # a bank's AdsrGatedPE(PeriodicGate) envelopes one block ahead on the side stream (render_mix)
 WIDE_SUPERSAW = True         # the bank kernel with 16 frames per thread (pgx_supersaw_wide) where its conditions hold
@@ -97,6 +97,134 @@ class _Rows:
         self.stride = total * ch
 
 
+def _param_records(dtype, pes, fields) -> np.ndarray:
+    """One record of `dtype` per PE, filled from the dict that `fields(pe)` returns."""
+    rec = np.zeros(len(pes), dtype=dtype)
+    for i, pe in enumerate(pes):
+        for key, v in fields(pe).items():
+            rec[i][key] = v
+    return rec
+
+
+def closed_form_ok(rec) -> bool:
+    """BLITSAW_PARAMS records whose integrator carries have a closed form -- the automatic (odd) M, a leak below 1: what
+    the kernels that cut an oscillator into concurrent time segments need."""
+    return bool(np.all(rec["m"] < 0.0) and np.all(rec["leak"] > 0.0) and np.all(rec["leak"] <= 0.9999)
+                and np.all(rec["freq"] >= 1.0))
+
+
+def _ensure_alt(*nodes) -> None:
+    """Double-buffered states: a kernel that runs in concurrent segments reads `state` and writes `state_alt` ..."""
+    for node in nodes:
+        if node.state_alt is None:
+            node.state_alt = DeviceBuffer(node.state.shape, node.state.dtype)
+
+
+def _swap_states(*nodes) -> None:
+    """... and the two change places behind it."""
+    for node in nodes:
+        node.state, node.state_alt = node.state_alt, node.state
+
+
+def _copy_state(dst, src) -> None:
+    check(lib().pgx_memcpy_d2d(dst.ptr, src.ptr, src.nbytes), "pgx_memcpy_d2d")
+
+
+class _Ahead:
+    """What a node rendered ahead of the stream: `data` for the frames (start, n); `undo()` puts back what that moved."""
+    __slots__ = ("start", "n", "data", "undo")
+
+    def __init__(self, start, n, data, undo=None):
+        self.start, self.n, self.data, self.undo = start, n, data, undo
+
+    def forget(self) -> None:
+        if self.undo is not None:
+            self.undo()
+
+    def take(self, start, n):
+        """`data` if it was rendered for these frames, else None: undone.  (The owner empties the slot either way.)"""
+        if self.start == start and self.n == n:
+            return self.data
+        self.forget()
+        return None
+
+
+class _StateBefore:
+    """The undo of oscillators that ran ahead: `node`'s states (a copy) and last_end from before."""
+    __slots__ = ("node", "state", "last_end")
+
+    def __init__(self, node, state=None):
+        self.node, self.last_end = node, node.last_end
+        self.state = state
+        if state is None:
+            self.state = DeviceBuffer(node.state.shape, node.state.dtype)
+            _copy_state(self.state, node.state)
+
+    def __call__(self) -> None:
+        _copy_state(self.node.state, self.state)
+        self.node.last_end = self.last_end
+
+
+class _Window:
+    """Several blocks of a stream rendered at once, handed out block by block: frames [first, end) in `buf`, blocks of
+    `block` frames, consumed up to `served`; `undo`: what the owner needs to go back to `first`."""
+    __slots__ = ("first", "end", "block", "buf", "served", "undo")
+
+    def __init__(self, first, blocks, block, buf, undo):
+        self.first, self.end, self.block, self.buf, self.undo = first, first + blocks * block, block, buf, undo
+        self.served = first + block
+
+
+class _Windowed:
+    """The 'stream of equal blocks -> windows of 2, 4, 8 ... blocks' machine of VoiceBank and _LadderNode.  The owner
+    decides whether a window may open, what to snapshot, how to restore and re-render; this keeps `win` (None: no window
+    is open), `last` -- (start, n) of the last block handed out --, `grow` and look-ahead's counters (bench.py: frames
+    rendered vs frames counted)."""
+
+    def _reset_windows(self, first_blocks: int) -> None:
+        self.win = None
+        self.last = None
+        self.grow = first_blocks
+
+    def _next_row(self, start, n):
+        """Offset of (start, n) in the open window's buffer if it is the window's next block, else None."""
+        win = self.win
+        if win is not None and start == win.served and n == win.block and start + n <= win.end:
+            win.served = start + n
+            self.last = (start, n)
+            return start - win.first
+        return None
+
+    def _continues(self, start, n) -> bool:
+        """Is (start, n) the block after the last one, same length?  It is the last one from here on."""
+        streaming = self.last == (start - n, n)
+        self.last = (start, n)
+        return streaming
+
+    def _window_blocks(self, n, max_blocks, max_frames) -> int:
+        """How many blocks of n frames to render at once (1: no window); the next window is twice as long."""
+        blocks = max(1, min(self.grow, max_frames // n))
+        if blocks > 1:
+            self.grow = min(self.grow * 2, max_blocks)
+        return blocks
+
+    def _open_window(self, start, blocks, n, buf, undo) -> None:
+        """(the first block is handed out by the caller)"""
+        from . import look_ahead as _look_ahead
+        _look_ahead.STATS["window_frames"] += n * blocks
+        _look_ahead.STATS["windows"] += 1
+        self.win = _Window(start, blocks, n, buf, undo)
+
+    def _close_window(self):
+        """No window is open afterwards.  -> (first, served, undo) if one was left half consumed -- the owner goes back to
+        `first` and renders [first, served) again, quietly (exact: the same kernels over the same frames) --, else None
+        (consumed to the last frame: the states are already there)."""
+        win, self.win = self.win, None
+        if win is None or win.served >= win.end:
+            return None
+        return win.first, win.served, win.undo
+
+
 class _Node:
     """One level of the voice tree: K PE instances of the same class and static config."""
 
@@ -116,13 +244,21 @@ class _Node:
     def quiesce(self, keep=None) -> None:
         """Anything rendered ahead of the stream is dropped: the states are where the last block handed out left them."""
 
+    def _forget_ahead(self, slot: str) -> None:
+        """What a node rendered ahead of the stream lives in a slot -- an attribute that holds an _Ahead, or None: empties
+        the slot and undoes what was ahead."""
+        ahead = getattr(self, slot)
+        if ahead is not None:
+            setattr(self, slot, None)
+            ahead.forget()
+
     def snapshot(self) -> dict:
         snap = {}
         for name in self._STATE:
             value = getattr(self, name)
             if isinstance(value, DeviceBuffer):
                 twin = DeviceBuffer(value.shape, value.dtype)
-                check(lib().pgx_memcpy_d2d(twin.ptr, value.ptr, value.nbytes), "pgx_memcpy_d2d")
+                _copy_state(twin, value)
                 value = twin
             snap[name] = value
         return snap
@@ -131,7 +267,7 @@ class _Node:
         for name, value in snap.items():
             mine = getattr(self, name)
             if isinstance(value, DeviceBuffer) and isinstance(mine, DeviceBuffer) and mine.shape == value.shape:
-                check(lib().pgx_memcpy_d2d(mine.ptr, value.ptr, value.nbytes), "pgx_memcpy_d2d")
+                _copy_state(mine, value)
             else:
                 setattr(self, name, value)
 
@@ -162,31 +298,28 @@ class _SineNode(_Node):
         return out
 
 
-class _BlitSawNode(_Node):
+class _SawNode(_Node):
+    """What the banks of BlitSawPEs (nv = 1) and of SuperSawPEs (nv oscillators per instance) share: `params`, `state`
+    and `init_state` are per oscillator; the reset rule; the fused bank kernels with their tables and double-buffered
+    states."""
+
     _STATE = ("state", "last_end")
 
-    def __init__(self, pes):
+    def __init__(self, pes, nv, rec, init_state):
         super().__init__(pes, {})
-        rec = np.zeros(self.k, dtype=_dev.BLITSAW_PARAMS)
-        for i, pe in enumerate(pes):
-            for key, v in pe._scalar_params().items():
-                rec[i][key] = v
+        self.nv = nv
         self.params = _dev.upload_structs(rec)
-        self.init_state = np.stack([pe._initial_state() for pe in pes])
-        self.state = DeviceBuffer((self.k, 2), np.float64)
+        self.init_state = init_state
+        self.state = DeviceBuffer((self.k * nv, 2), np.float64)
+        self.state_alt = None        # the segmented bank reads one state buffer and writes the other
         self.ch = pes[0]._channels
         self.last_end = None
-        # a few oscillators in concurrent time segments: the SuperSaw bank kernel with one voice per instance
-        # (_SuperSawNode.segmented); needs the automatic (odd) M and a leak below 1 for the closed-form carries
-        self.closed_form_ok = bool(np.all(rec["m"] < 0.0) and np.all(rec["leak"] > 0.0)
-                                   and np.all(rec["leak"] <= 0.9999) and np.all(rec["freq"] >= 1.0))
-        self.wide_ok = wide_oscillators_ok(rec, self.sr)           # (_SuperSawNode.wide)
-        self.state_alt = None
-        self.tables = {}
-        self.unit_amp = None
-
-    def reset(self):
-        self.last_end = None
+        # a few instances in concurrent time segments (segmented): needs the integrator's closed-form carries
+        self.closed_form_ok = closed_form_ok(rec)
+        # pgx_supersaw_wide (16 frames per thread): the rotation / recurrence form of the Dirichlet kernel only -- scalar
+        # frequency, the automatic M -- and the closed-form carries of the time segments (blit_saw_pe.wide_oscillators_ok)
+        self.wide_ok = wide_oscillators_ok(rec, self.sr)
+        self.tables = {}             # what depends on the parameters only (pgx_supersaw_*_tables), made on first use
 
     def channels(self):
         return self.ch
@@ -197,41 +330,70 @@ class _BlitSawNode(_Node):
             self.state.upload(self.init_state)
 
     def wide(self) -> bool:
-        return WIDE_SUPERSAW and self.wide_ok
+        return WIDE_SUPERSAW and self.wide_ok and self.nv <= 16
+
+    SEGMENTED_MIN = 0            # instances from which the bank is cut into time segments
 
     def segmented(self, n: int) -> bool:
+        """Fewer instances than fill the chip (a rank's share of a sharded mix; a few BlitSawPEs -- the SuperSaw bank
+        kernel with one voice per instance): the fused bank in concurrent time segments (pgx_supersaw_wide /
+        pgx_supersaw_bank_seg), carries from the integrator's closed form -- automatic (odd) M, leak < 1."""
         L = lib()
-        segments = (L.pgx_supersaw_wide_segments(self.k, 1, n) if self.wide()
+        segments = (L.pgx_supersaw_wide_segments(self.k, self.nv, n) if self.wide()
                     else L.pgx_supersaw_bank_segments(self.k, n))
-        return SEGMENTED_SUPERSAW and self.closed_form_ok and 4 <= self.k < FUSED_SUPERSAW_MIN and segments > 1
+        return (SEGMENTED_SUPERSAW and self.SEGMENTED_MIN <= self.k < FUSED_SUPERSAW_MIN and self.nv <= 16
+                and self.closed_form_ok and segments > 1)
+
+    def saw_tables(self, kind: str) -> DeviceBuffer:
+        """The per-oscillator tables of pgx_supersaw_wide ("wide") or pgx_supersaw_bank_seg ("bank")."""
+        tables = self.tables.get(kind)
+        if tables is None:
+            L = lib()
+            size, make = ((L.pgx_supersaw_wide_table_bytes, L.pgx_supersaw_wide_tables) if kind == "wide"
+                          else (L.pgx_supersaw_bank_table_bytes, L.pgx_supersaw_bank_tables))
+            tables = self.tables[kind] = DeviceBuffer((size(self.k, self.nv),), np.uint8)
+            check(make(tables.ptr, self.k, self.nv, self.sr, self.params.ptr), f"pgx_supersaw_{kind}_tables")
+        return tables
+
+    def _render_bank(self, start, n, amp):
+        """[instances][n][channels], the oscillators of an instance summed on chip and scaled by `amp`, on the current
+        stream; the states move from `state` to `state_alt` and swap.  The caller has prepared the states."""
+        L = lib()
+        if self.state_alt is None:
+            _ensure_alt(self)
+        kind = "wide" if self.wide() else "bank"
+        tables = self.saw_tables(kind)
+        out = DeviceBuffer((self.k, n, self.ch), np.float32)
+        if kind == "wide":
+            check(L.pgx_supersaw_wide(out.ptr, n * self.ch, self.k, self.nv, n, self.ch, self.state.ptr,
+                                      self.state_alt.ptr, amp.ptr, tables.ptr), "pgx_supersaw_wide")
+        else:
+            check(L.pgx_supersaw_bank_seg(out.ptr, n * self.ch, self.k, self.nv, n, self.ch, self.sr,
+                                          self.params.ptr, self.state.ptr, self.state_alt.ptr, amp.ptr,
+                                          tables.ptr), "pgx_supersaw_bank_seg")
+        _swap_states(self)
+        self.last_end = start + n
+        return out
+
+
+class _BlitSawNode(_SawNode):
+    SEGMENTED_MIN = 4
+
+    def __init__(self, pes):
+        rec = _param_records(_dev.BLITSAW_PARAMS, pes, lambda pe: pe._scalar_params())
+        super().__init__(pes, 1, rec, np.stack([pe._initial_state() for pe in pes]))
+        self.unit_amp = None
+
+    def reset(self):
+        self.last_end = None
 
     def _render_segments(self, start, n):
         """The SuperSaw bank kernels with one voice per instance and unit instance amplitude: float32(y * 2 amp * 1.0)
         is the oscillator's own sample (pgx_supersaw_wide; pgx_supersaw_bank_seg rounds to float32 twice, the same)."""
-        L = lib()
         self.prepare(start)
-        if self.state_alt is None:
-            self.state_alt = DeviceBuffer(self.state.shape, self.state.dtype)
         if self.unit_amp is None:
             self.unit_amp = DeviceBuffer.from_host(np.ones(self.k, dtype=np.float64))
-        kind = "wide" if self.wide() else "bank"
-        tables = self.tables.get(kind)
-        if tables is None:
-            size, make = ((L.pgx_supersaw_wide_table_bytes, L.pgx_supersaw_wide_tables) if kind == "wide"
-                          else (L.pgx_supersaw_bank_table_bytes, L.pgx_supersaw_bank_tables))
-            tables = self.tables[kind] = DeviceBuffer((size(self.k, 1),), np.uint8)
-            check(make(tables.ptr, self.k, 1, self.sr, self.params.ptr), f"pgx_supersaw_{kind}_tables")
-        out = DeviceBuffer((self.k, n, self.ch), np.float32)
-        if kind == "wide":
-            check(L.pgx_supersaw_wide(out.ptr, n * self.ch, self.k, 1, n, self.ch, self.state.ptr,
-                                      self.state_alt.ptr, self.unit_amp.ptr, tables.ptr), "pgx_supersaw_wide")
-        else:
-            check(L.pgx_supersaw_bank_seg(out.ptr, n * self.ch, self.k, 1, n, self.ch, self.sr, self.params.ptr,
-                                          self.state.ptr, self.state_alt.ptr, self.unit_amp.ptr, tables.ptr),
-                  "pgx_supersaw_bank_seg")
-        self.state, self.state_alt = self.state_alt, self.state
-        self.last_end = start + n
-        return out
+        return self._render_bank(start, n, self.unit_amp)
 
     def render(self, start, n):
         if self.segmented(n):
@@ -245,77 +407,42 @@ class _BlitSawNode(_Node):
         return out
 
 
-class _SuperSawNode(_Node):
+class _SuperSawNode(_SawNode):
     """Bank of SuperSawPEs.  From FUSED_SUPERSAW_MIN instances on: one launch, voices summed on chip.  Below
     (a rank's share of a sharded mix): the oscillators of all instances in one launch (`_voices`), then the
     ordered voice sum.  When the node feeds the bank's mix directly VoiceBank pipelines the two (see
-    VoiceBank._supersaw_pipelined): `ahead` then holds the oscillator samples of the block after the last one."""
-
-    _STATE = ("state", "last_end")
-
-    def quiesce(self, keep=None):
-        self._forget_ahead(restore=True)
-        if self.ahead_bank is not None:
-            self._forget_bank_ahead(restore=True)
+    VoiceBank._supersaw_pipelined): `ahead` then holds the oscillator samples of the block after the last one,
+    or `ahead_bank` the bank's output for it."""
 
     def __init__(self, pes):
-        super().__init__(pes, {})
-        self.nv = len(pes[0]._oscillators)
-        self.params = _dev.upload_structs(np.concatenate([pe._voice_param_records() for pe in pes]))
-        self.init_state = np.concatenate([pe._voice_initial_state() for pe in pes])
-        self.state = DeviceBuffer((self.k * self.nv, 2), np.float64)
-        self.amp = DeviceBuffer.from_host(np.array([float(pe._amplitude) for pe in pes], dtype=np.float64))
-        self.ch = pes[0]._channels
-        self.last_end = None
-        self.ahead = None            # (start, n, voices buffer, (state copy, last_end))
         rec = np.concatenate([pe._voice_param_records() for pe in pes])
-        self.closed_form_ok = bool(np.all(rec["m"] < 0.0) and np.all(rec["leak"] > 0.0)
-                                   and np.all(rec["leak"] <= 0.9999) and np.all(rec["freq"] >= 1.0))
-        # pgx_supersaw_wide (16 frames per thread): the rotation / recurrence form of the Dirichlet kernel only -- scalar
-        # frequency, the automatic M -- and the closed-form carries of the time segments (blit_saw_pe.wide_oscillators_ok)
-        self.wide_ok = wide_oscillators_ok(rec, self.sr)
-        self.state_alt = None        # the segmented bank reads one state buffer and writes the other
-        self.ahead_bank = None       # (start, n, bank output, last_end before): VoiceBank._supersaw_pipelined
-        self.tables = {}             # ... and loads what depends on the parameters only (pgx_supersaw_*_tables)
+        super().__init__(pes, len(pes[0]._oscillators), rec, np.concatenate([pe._voice_initial_state() for pe in pes]))
+        self.amp = DeviceBuffer.from_host(np.array([float(pe._amplitude) for pe in pes], dtype=np.float64))
+        self.ahead = None            # _Ahead(voices buffer; undo: the states and last_end from before)
+        self.ahead_bank = None       # _Ahead(bank output; undo: the states swapped back, last_end from before)
+
+    def quiesce(self, keep=None):
+        self._forget_ahead("ahead")
+        self._forget_ahead("ahead_bank")
+
+    def reset(self):
+        self.ahead = self.ahead_bank = None
+        self.last_end = None
 
     def fused(self) -> bool:
         return self.k >= FUSED_SUPERSAW_MIN and self.nv <= 16
 
-    def wide(self) -> bool:
-        return WIDE_SUPERSAW and self.wide_ok and self.nv <= 16
-
-    def segmented(self, n: int) -> bool:
-        """Fewer instances than fill the chip (a rank's share of a sharded mix): the fused bank in concurrent time
-        segments (pgx_supersaw_wide / pgx_supersaw_bank_seg), carries from the integrator's closed form -- automatic
-        (odd) M, leak < 1."""
-        L = lib()
-        segments = (L.pgx_supersaw_wide_segments(self.k, self.nv, n) if self.wide()
-                    else L.pgx_supersaw_bank_segments(self.k, n))
-        return (SEGMENTED_SUPERSAW and not self.fused() and self.nv <= 16 and self.closed_form_ok
-                and segments > 1)
-
-    def _forget_ahead(self, restore: bool) -> None:
-        ahead, self.ahead = self.ahead, None
-        if ahead is not None and restore:
-            saved, last_end = ahead[3]
-            check(lib().pgx_memcpy_d2d(self.state.ptr, saved.ptr, saved.nbytes), "pgx_memcpy_d2d")
-            self.last_end = last_end
-
-    def reset(self):
-        self._forget_ahead(restore=False)
-        self.ahead_bank = None
-        self.last_end = None
-
-    def channels(self):
-        return self.ch
+    def banked(self, n: int) -> bool:
+        """The voices-summed-on-chip kernel with per-voice tables and double-buffered states (pgx_supersaw_bank_seg):
+        in time segments for a few instances, one segment each from FUSED_SUPERSAW_MIN instances on."""
+        return self.segmented(n) or (self.fused() and self.closed_form_ok)
 
     def _voices(self, start, n, backup=None):
         """[instances * voices][n] float32 oscillator samples, on the current stream.  backup: a buffer that
         receives the states on entry (written by the oscillator kernel itself: no extra launch)."""
         if self.ahead_bank is not None:
-            self._forget_bank_ahead(restore=True)
-        if self.last_end is None or start != self.last_end:
-            self.state.upload(self.init_state)
+            self._forget_ahead("ahead_bank")
+        self.prepare(start)
         voices = DeviceBuffer((self.k * self.nv, n), np.float32)
         ws = blitsaw_workspace(self, self.k * self.nv, n, False)
         check(lib().pgx_blitsaw(voices.ptr, n, self.k * self.nv, n, 1, self.sr, self.params.ptr,
@@ -326,17 +453,13 @@ class _SuperSawNode(_Node):
     def take_voices(self, start, n):
         """The oscillator samples of (start, n): the ones rendered ahead if they are these, else rendered now
         (after the states went back to where the caller's last block left them)."""
-        if self.ahead is not None:
-            if self.ahead[0] == start and self.ahead[1] == n:
-                voices, self.ahead = self.ahead[2], None
-                return voices
-            self._forget_ahead(restore=True)
-        return self._voices(start, n)
+        voices = self.ahead.take(start, n) if self.ahead is not None else None
+        self.ahead = None
+        return voices if voices is not None else self._voices(start, n)
 
     def render_ahead(self, start, n) -> None:
-        saved = DeviceBuffer(self.state.shape, self.state.dtype)
-        last_end = self.last_end
-        self.ahead = (start, n, self._voices(start, n, backup=saved), (saved, last_end))
+        undo = _StateBefore(self, state=DeviceBuffer(self.state.shape, self.state.dtype))
+        self.ahead = _Ahead(start, n, self._voices(start, n, backup=undo.state), undo)
 
     def sum_voices(self, voices, n):
         out = DeviceBuffer((self.k, n, self.ch), np.float32)
@@ -344,73 +467,39 @@ class _SuperSawNode(_Node):
                                      self.amp.ptr, None, 0), "pgx_supersaw_sum")
         return out
 
-    def banked(self, n: int) -> bool:
-        """The voices-summed-on-chip kernel with per-voice tables and double-buffered states (pgx_supersaw_bank_seg):
-        in time segments for a few instances, one segment each from FUSED_SUPERSAW_MIN instances on."""
-        return self.segmented(n) or (self.fused() and self.closed_form_ok)
-
     def _bank(self, start, n):
         """[instances][n][channels] on the current stream; the states move from `state` to `state_alt` and swap."""
-        L = lib()
         if self.ahead is not None:
-            self._forget_ahead(restore=True)
-        if self.last_end is None or start != self.last_end:
-            self.state.upload(self.init_state)
-        if self.state_alt is None:
-            self.state_alt = DeviceBuffer(self.state.shape, self.state.dtype)
-        kind = "wide" if self.wide() else "bank"
-        tables = self.tables.get(kind)
-        if tables is None:
-            size, make = ((L.pgx_supersaw_wide_table_bytes, L.pgx_supersaw_wide_tables) if kind == "wide"
-                          else (L.pgx_supersaw_bank_table_bytes, L.pgx_supersaw_bank_tables))
-            tables = self.tables[kind] = DeviceBuffer((size(self.k, self.nv),), np.uint8)
-            check(make(tables.ptr, self.k, self.nv, self.sr, self.params.ptr), f"pgx_supersaw_{kind}_tables")
-        out = DeviceBuffer((self.k, n, self.ch), np.float32)
-        if kind == "wide":
-            check(L.pgx_supersaw_wide(out.ptr, n * self.ch, self.k, self.nv, n, self.ch, self.state.ptr,
-                                      self.state_alt.ptr, self.amp.ptr, tables.ptr), "pgx_supersaw_wide")
-        else:
-            check(L.pgx_supersaw_bank_seg(out.ptr, n * self.ch, self.k, self.nv, n, self.ch, self.sr,
-                                          self.params.ptr, self.state.ptr, self.state_alt.ptr, self.amp.ptr,
-                                          tables.ptr), "pgx_supersaw_bank_seg")
-        self.state, self.state_alt = self.state_alt, self.state
-        self.last_end = start + n
-        return out
+            self._forget_ahead("ahead")
+        self.prepare(start)
+        return self._render_bank(start, n, self.amp)
 
-    def _forget_bank_ahead(self, restore: bool) -> None:
-        ahead, self.ahead_bank = self.ahead_bank, None
-        if ahead is not None and restore:
-            # one render happened since: the states it started from are the other buffer
-            self.state, self.state_alt = self.state_alt, self.state
-            self.last_end = ahead[3]
+    def _bank_undo(self, last_end) -> None:
+        _swap_states(self)           # one render happened since: the states it started from are the other buffer
+        self.last_end = last_end
 
     def take_bank(self, start, n):
         """The bank's output for (start, n): the block rendered ahead if it is this one, else rendered now (after the
         states went back to where the caller's last block left them)."""
-        if self.ahead_bank is not None:
-            if self.ahead_bank[0] == start and self.ahead_bank[1] == n:
-                out, self.ahead_bank = self.ahead_bank[2], None
-                return out
-            self._forget_bank_ahead(restore=True)
-        return self._bank(start, n)
+        out = self.ahead_bank.take(start, n) if self.ahead_bank is not None else None
+        self.ahead_bank = None
+        return out if out is not None else self._bank(start, n)
 
     def render_bank_ahead(self, start, n) -> None:
-        last_end = self.last_end
-        self.ahead_bank = (start, n, self._bank(start, n), last_end)
+        undo = functools.partial(self._bank_undo, self.last_end)
+        self.ahead_bank = _Ahead(start, n, self._bank(start, n), undo)
 
     def render(self, start, n):
-        L = lib()
         if self.banked(n):
             return self.take_bank(start, n)
         if self.ahead_bank is not None:
-            self._forget_bank_ahead(restore=True)
+            self._forget_ahead("ahead_bank")
         if self.fused():
             # enough instances to fill the chip with one wave per oscillator: voices summed on chip
-            if self.last_end is None or start != self.last_end:
-                self.state.upload(self.init_state)
+            self.prepare(start)
             out = DeviceBuffer((self.k, n, self.ch), np.float32)
-            check(L.pgx_supersaw_bank(out.ptr, n * self.ch, self.k, self.nv, n, self.ch, self.sr,
-                                      self.params.ptr, self.state.ptr, self.amp.ptr), "pgx_supersaw_bank")
+            check(lib().pgx_supersaw_bank(out.ptr, n * self.ch, self.k, self.nv, n, self.ch, self.sr,
+                                          self.params.ptr, self.state.ptr, self.amp.ptr), "pgx_supersaw_bank")
             self.last_end = start + n
             return out
         return self.sum_voices(self.take_voices(start, n), n)
@@ -467,22 +556,27 @@ class _BiquadNode(_Node):
         mine = self.entries_ahead.get(keep[0]) if keep is not None else None
         self.entries_ahead = {keep[0]: mine} if mine is not None and mine[0] == keep[1] else {}
 
-    def _mix_tables(self):
-        L = lib()
-        src = self.children["source"]
-        saw_tables = src.tables.get("wide")
-        if saw_tables is None:
-            saw_tables = src.tables["wide"] = DeviceBuffer((L.pgx_supersaw_wide_table_bytes(self.k, 1),), np.uint8)
-            check(L.pgx_supersaw_wide_tables(saw_tables.ptr, self.k, 1, self.sr, src.params.ptr),
-                  "pgx_supersaw_wide_tables")
+    def _ensure_state(self, ch: int) -> None:
+        if self.state is None:
+            self.state = DeviceBuffer((self.k, ch, 2), np.float64, zero=True)
+
+    def _power_tables(self) -> DeviceBuffer:
+        """Per-voice powers of A (pgx_biquad_tables), made on first use."""
         if self.tables is None:
+            L = lib()
             self.tables = DeviceBuffer((self.k, L.pgx_biquad_table_doubles()), np.float64)
             check(L.pgx_biquad_tables(self.tables.ptr, self.coef.ptr, self.k), "pgx_biquad_tables")
+        return self.tables
+
+    def _mix_tables(self) -> DeviceBuffer:
         if self.rot_tables is None:
+            L = lib()
+            saw_tables, tables = self.children["source"].saw_tables("wide"), self._power_tables()
             assert L.pgx_voice_tiles_max_warm() == VOICE_TILES_MAX_WARM
             self.rot_tables = DeviceBuffer((L.pgx_voice_tiles_table_bytes(self.k),), np.uint8)
-            check(L.pgx_voice_tiles_tables(self.rot_tables.ptr, saw_tables.ptr, self.coef.ptr, self.tables.ptr, self.k),
+            check(L.pgx_voice_tiles_tables(self.rot_tables.ptr, saw_tables.ptr, self.coef.ptr, tables.ptr, self.k),
                   "pgx_voice_tiles_tables")
+        return self.rot_tables
 
     def render_mix(self, start, n, gain=None, streaming=False):
         """The voices' mix (times `gain`, [K][n] float32, voice by voice) as one (n, 1) block.  streaming: (start + n, n)
@@ -490,12 +584,8 @@ class _BiquadNode(_Node):
         in the launch that adds this block's rows, off the next block's critical chain."""
         L = lib()
         src = self.children["source"]
-        if self.state is None:
-            self.state = DeviceBuffer((self.k, 1, 2), np.float64, zero=True)
-        if self.state_alt is None:
-            self.state_alt = DeviceBuffer(self.state.shape, np.float64)
-        if src.state_alt is None:
-            src.state_alt = DeviceBuffer(src.state.shape, src.state.dtype)
+        self._ensure_state(1)
+        _ensure_alt(self, src)
         slot = -1
         mine = self.entries_ahead.pop(start, None)
         if mine is not None and mine[0] == n and src.last_end == start:
@@ -504,82 +594,55 @@ class _BiquadNode(_Node):
         if stale:
             self.entries_ahead = {}
         src.prepare(start)
-        self._mix_tables()
+        rot_tables = self._mix_tables()
         need = L.pgx_voice_tiles_workspace_bytes(self.k, n, self.settle_fine)
         if self.tiles_ws is None or self.tiles_ws.nbytes < need:
             self.tiles_ws = DeviceBuffer((need,), np.uint8)
             slot = -1
         out = DeviceBuffer((n, 1), np.float32)
         nxt = ((slot if slot >= 0 else 0) ^ 1) if streaming else -1
-        check(L.pgx_voice_tiles(out.ptr, self.k, n, self.rot_tables.ptr, src.state.ptr, src.state_alt.ptr,
+        check(L.pgx_voice_tiles(out.ptr, self.k, n, rot_tables.ptr, src.state.ptr, src.state_alt.ptr,
                                 self.state.ptr, self.state_alt.ptr, ptr(gain), n, self.settle_fine, self.tiles_ws.ptr,
                                 slot, nxt), "pgx_voice_tiles")
         if streaming:
             self.entries_ahead[start + n] = (n, nxt)
-        src.state, src.state_alt = src.state_alt, src.state
-        self.state, self.state_alt = self.state_alt, self.state
+        _swap_states(src, self)
         src.last_end = start + n
         return out
 
-    def takes_gain(self) -> bool:
-        """render(..., gain=<[K][n] float32>) multiplies the voices by it inside the chain's kernel."""
-        src = self.children["source"]
-        return isinstance(src, _BlitSawNode) and src.ch == 1 and self.k >= FUSED_VOICE_MIN and src.wide()
-
-    def _render_chain_segments(self, start, n, gain=None):
+    def _render_chain_segments(self, start, n):
         """A small bank (a rank's share of C5): oscillator -> filter as ONE launch in concurrent time segments instead of
         the segmented oscillator bank followed by the batched settled biquad (two kernels and the dispatch gap between
         them on the block's critical chain).  States are read from one buffer and written to another."""
         L = lib()
         src = self.children["source"]
-        if self.state is None:
-            self.state = DeviceBuffer((self.k, 1, 2), np.float64, zero=True)
-        if self.state_alt is None:
-            self.state_alt = DeviceBuffer(self.state.shape, np.float64)
-        if src.state_alt is None:
-            src.state_alt = DeviceBuffer(src.state.shape, src.state.dtype)
+        self._ensure_state(1)
+        _ensure_alt(self, src)
         src.prepare(start)
-        saw_tables = src.tables.get("wide")
-        if saw_tables is None:
-            saw_tables = src.tables["wide"] = DeviceBuffer((L.pgx_supersaw_wide_table_bytes(self.k, 1),), np.uint8)
-            check(L.pgx_supersaw_wide_tables(saw_tables.ptr, self.k, 1, self.sr, src.params.ptr),
-                  "pgx_supersaw_wide_tables")
-        if self.tables is None:
-            self.tables = DeviceBuffer((self.k, L.pgx_biquad_table_doubles()), np.float64)
-            check(L.pgx_biquad_tables(self.tables.ptr, self.coef.ptr, self.k), "pgx_biquad_tables")
+        saw_tables, tables = src.saw_tables("wide"), self._power_tables()
         out = DeviceBuffer((self.k, n, 1), np.float32)
         check(L.pgx_blitsaw_biquad_wide_seg(out.ptr, n, self.k, n, saw_tables.ptr, src.state.ptr, src.state_alt.ptr,
-                                            self.coef.ptr, self.tables.ptr, self.state.ptr, self.state_alt.ptr,
-                                            ptr(gain), n, self.settle), "pgx_blitsaw_biquad_wide_seg")
-        src.state, src.state_alt = src.state_alt, src.state
-        self.state, self.state_alt = self.state_alt, self.state
+                                            self.coef.ptr, tables.ptr, self.state.ptr, self.state_alt.ptr,
+                                            None, n, self.settle), "pgx_blitsaw_biquad_wide_seg")
+        _swap_states(src, self)
         src.last_end = start + n
         return out
 
-    def render(self, start, n, gain=None):
+    def render(self, start, n):
         L = lib()
         src = self.children["source"]
         if self._chain_segments(n):
-            return self._render_chain_segments(start, n, gain)
+            return self._render_chain_segments(start, n)
         if isinstance(src, _BlitSawNode) and src.ch == 1 and self.k >= FUSED_VOICE_MIN:
             # oscillator -> filter without the [K][frames] oscillator buffer (pgx_blitsaw_biquad_bank)
-            if self.state is None:
-                self.state = DeviceBuffer((self.k, 1, 2), np.float64, zero=True)
+            self._ensure_state(1)
             src.prepare(start)
             out = DeviceBuffer((self.k, n, 1), np.float32)
             if src.wide():
                 # sixteen frames per thread (pgx_blitsaw_biquad_wide): the oscillator's and the filter's per-voice tables
-                saw_tables = src.tables.get("wide")
-                if saw_tables is None:
-                    saw_tables = src.tables["wide"] = DeviceBuffer((L.pgx_supersaw_wide_table_bytes(self.k, 1),), np.uint8)
-                    check(L.pgx_supersaw_wide_tables(saw_tables.ptr, self.k, 1, self.sr, src.params.ptr),
-                          "pgx_supersaw_wide_tables")
-                if self.tables is None:
-                    self.tables = DeviceBuffer((self.k, L.pgx_biquad_table_doubles()), np.float64)
-                    check(L.pgx_biquad_tables(self.tables.ptr, self.coef.ptr, self.k), "pgx_biquad_tables")
+                saw_tables, tables = src.saw_tables("wide"), self._power_tables()
                 check(L.pgx_blitsaw_biquad_wide(out.ptr, n, self.k, n, saw_tables.ptr, src.state.ptr, self.coef.ptr,
-                                                self.tables.ptr, self.state.ptr, ptr(gain), n),
-                      "pgx_blitsaw_biquad_wide")
+                                                tables.ptr, self.state.ptr, None, n), "pgx_blitsaw_biquad_wide")
             else:
                 check(L.pgx_blitsaw_biquad_bank(out.ptr, n, self.k, n, self.sr, src.params.ptr, src.state.ptr,
                                                 self.coef.ptr, self.state.ptr), "pgx_blitsaw_biquad_bank")
@@ -587,22 +650,19 @@ class _BiquadNode(_Node):
             return out
         x = src.render(start, n)
         ch = x.shape[2]
-        if self.state is None:
-            self.state = DeviceBuffer((self.k, ch, 2), np.float64, zero=True)
-        if self.tables is None:
-            self.tables = DeviceBuffer((self.k, L.pgx_biquad_table_doubles()), np.float64)
-            check(L.pgx_biquad_tables(self.tables.ptr, self.coef.ptr, self.k), "pgx_biquad_tables")
+        self._ensure_state(ch)
+        tables = self._power_tables()
         need = L.pgx_biquad_workspace_bytes(self.k, n, ch, self.settle)
         if need and (self.ws is None or self.ws.nbytes < need):
             self.ws = DeviceBuffer((need,), np.uint8)
         out = DeviceBuffer((self.k, n, ch), np.float32)
         check(L.pgx_biquad_const(out.ptr, n * ch, x.ptr, n * ch, self.k, n, ch, self.coef.ptr,
-                                 self.tables.ptr, self.settle, self.state.ptr, ptr(self.ws) if need else None),
+                                 tables.ptr, self.settle, self.state.ptr, ptr(self.ws) if need else None),
               "pgx_biquad_const")
         return out
 
 
-class _LadderNode(_Node):
+class _LadderNode(_Windowed, _Node):
     """Bank of LadderPEs.  The ladder kernel is latency-bound (two waves per CU, most of the chip idle) and its
     input, a bank of scalar oscillators, is a pure function of time plus a few carried numbers -- so while block k
     goes through the ladder on the main stream, the oscillators of block k+1 are rendered on the side stream.
@@ -613,15 +673,11 @@ class _LadderNode(_Node):
 
     def quiesce(self, keep=None):
         self._settle_window()
-        self._forget_ahead(restore=True)
+        self._forget_ahead("ahead")
 
     def __init__(self, pes, children):
         super().__init__(pes, children)
-        rec = np.zeros(self.k, dtype=_dev.LADDER_PARAMS)
-        for i, pe in enumerate(pes):
-            for key, v in pe._scalar_params().items():
-                rec[i][key] = v
-        self.params = _dev.upload_structs(rec)
+        self.params = _dev.upload_structs(_param_records(_dev.LADDER_PARAMS, pes, lambda pe: pe._scalar_params()))
         self.state = None
         self.ws = None
         settles = [pe._settle_frames() for pe in pes]
@@ -631,11 +687,9 @@ class _LadderNode(_Node):
         # device check decides (ladder_pe.SettleOptimist) -- an oscillator bank locks a saturating ladder to itself
         from .ladder_pe import SettleOptimist
         self.optimist = SettleOptimist() if self.settle == 0 else None
-        self.ahead = None          # (start, n, input buffer, (state copy, last_end)) rendered ahead of the caller
+        self.ahead = None          # _Ahead(the input rendered ahead of the caller; undo: the oscillators' _StateBefore)
         self.is_root = False       # directly under the bank's mix: may hand out rows of a window (VoiceBank.__init__)
-        self.win = None            # [first, end, n, buffer, served, (ladder state, oscillator state, last_end)]
-        self.last = None           # (start, n) of the last block handed out
-        self.grow = LADDER_WINDOW_FIRST
+        self._reset_windows(LADDER_WINDOW_FIRST)     # win.undo: (ladder state, the oscillators' _StateBefore)
 
     # ---- windows (root node only).  A lane of k_ladder_segments integrates 1024 warm-up samples to emit its share of the
     # block -- 94 frames of a 48 000-frame block of 64 instances: 92 % of the work is warm-up.  A stream of equal blocks
@@ -643,70 +697,51 @@ class _LadderNode(_Node):
     # out block by block as rows of that window.  A pull that is not the next block puts the states back to the
     # window's start and renders the consumed part again, quietly (exact: the same kernels over the same frames).
     def _settle_window(self) -> None:
-        win, self.win = self.win, None
-        if win is None:
+        left = self._close_window()
+        if left is None:
             return
-        first, end, n, buf, served, (ladder_state, osc_state, osc_last_end) = win
-        if served >= end:
-            return                                       # consumed to the last frame: the states are already there
-        self._forget_ahead(restore=False)
-        src = self.children["source"]
-        check(lib().pgx_memcpy_d2d(self.state.ptr, ladder_state.ptr, ladder_state.nbytes), "pgx_memcpy_d2d")
-        check(lib().pgx_memcpy_d2d(src.state.ptr, osc_state.ptr, osc_state.nbytes), "pgx_memcpy_d2d")
-        src.last_end = osc_last_end
+        first, served, (ladder_state, oscillators_before) = left
+        self.ahead = None                                # (the oscillators go back further than that)
+        _copy_state(self.state, ladder_state)
+        oscillators_before()
         if served > first:
             self._render_now(first, served - first)
 
     def render(self, start, n):
-        win = self.win
-        if win is not None:
-            if start == win[4] and n == win[2] and start + n <= win[1]:
-                win[4] = start + n
-                self.last = (start, n)
-                return _Rows(win[3], start - win[0], n)
+        offset = self._next_row(start, n)
+        if offset is not None:
+            return _Rows(self.win.buf, offset, n)
+        closed = self.win          # (held to the end of this pull: its buffers return to the pool behind what is enqueued here)
+        if closed is not None:
             self._settle_window()
-        streaming = self.last == (start - n, n)
-        self.last = (start, n)
+        streaming = self._continues(start, n)
         src = self.children["source"]
         if (LADDER_WINDOWS and self.is_root and streaming and n >= 4096 and self.state is not None
-                and isinstance(src, (_SuperSawNode, _BlitSawNode)) and not lib().pgx_stream_is_forked()):
-            blocks = max(1, min(self.grow, LADDER_WINDOW_FRAMES // n))
+                and isinstance(src, _SawNode) and not lib().pgx_stream_is_forked()):
+            blocks = self._window_blocks(n, LADDER_WINDOW_MAX, LADDER_WINDOW_FRAMES)
             if blocks > 1:
-                self.grow = min(self.grow * 2, LADDER_WINDOW_MAX)
-                if self.ahead is not None and not (self.ahead[0] == start and self.ahead[1] == n * blocks):
-                    self._forget_ahead(restore=True)
-                L = lib()
-                snap = (DeviceBuffer(self.state.shape, self.state.dtype), DeviceBuffer(src.state.shape, src.state.dtype))
-                check(L.pgx_memcpy_d2d(snap[0].ptr, self.state.ptr, snap[0].nbytes), "pgx_memcpy_d2d")
-                if self.ahead is not None:               # the oscillators already ran on: their states before that
-                    check(L.pgx_memcpy_d2d(snap[1].ptr, self.ahead[3][0].ptr, snap[1].nbytes), "pgx_memcpy_d2d")
-                    osc_last_end = self.ahead[3][1]
+                ahead = self.ahead
+                if ahead is not None and not (ahead.start == start and ahead.n == n * blocks):
+                    self._forget_ahead("ahead")
+                    ahead = None
+                ladder_state = DeviceBuffer(self.state.shape, self.state.dtype)
+                _copy_state(ladder_state, self.state)
+                if ahead is not None:                    # the oscillators already ran on: their states before that
+                    before = _StateBefore(src, state=DeviceBuffer(src.state.shape, src.state.dtype))
+                    _copy_state(before.state, ahead.undo.state)
+                    before.last_end = ahead.undo.last_end
                 else:
-                    check(L.pgx_memcpy_d2d(snap[1].ptr, src.state.ptr, snap[1].nbytes), "pgx_memcpy_d2d")
-                    osc_last_end = src.last_end
+                    before = _StateBefore(src)
                 big = self._render_now(start, n * blocks)
-                from . import look_ahead as _look_ahead
-                _look_ahead.STATS["window_frames"] += n * blocks          # (bench.py: frames rendered vs frames counted)
-                _look_ahead.STATS["windows"] += 1
-                self.win = [start, start + n * blocks, n, big, start + n, (snap[0], snap[1], osc_last_end)]
+                self._open_window(start, blocks, n, big, (ladder_state, before))
                 return _Rows(big, 0, n)
         else:
             self.grow = LADDER_WINDOW_FIRST
         return self._render_now(start, n)
 
-    def _forget_ahead(self, restore: bool) -> None:
-        ahead, self.ahead = self.ahead, None
-        if ahead is not None and restore:
-            src = self.children["source"]
-            saved, last_end = ahead[3]
-            check(lib().pgx_memcpy_d2d(src.state.ptr, saved.ptr, saved.nbytes), "pgx_memcpy_d2d")
-            src.last_end = last_end
-
     def reset(self):
-        self.win = None
-        self.last = None
-        self.grow = LADDER_WINDOW_FIRST
-        self._forget_ahead(restore=False)            # the oscillators start over anyway
+        self._reset_windows(LADDER_WINDOW_FIRST)
+        self.ahead = None                            # (nothing to undo: the oscillators start over anyway)
         super().reset()
         if self.state is not None:
             self.state.zero_()
@@ -717,12 +752,8 @@ class _LadderNode(_Node):
     def _render_now(self, start, n):
         L = lib()
         src = self.children["source"]
-        x = None
-        if self.ahead is not None:
-            if self.ahead[0] == start and self.ahead[1] == n:
-                x, self.ahead = self.ahead[2], None
-            else:
-                self._forget_ahead(restore=True)
+        x = self.ahead.take(start, n) if self.ahead is not None else None
+        self.ahead = None
         if x is None:
             x = src.render(start, n)
         ch = x.shape[2]
@@ -746,7 +777,7 @@ class _LadderNode(_Node):
             if self.optimist is not None and need and settle:
                 self.optimist.launched(self.ws, settle, n, self.k * ch)
 
-        speculate = (PREFETCH_LADDER_INPUT and isinstance(src, (_SuperSawNode, _BlitSawNode)) and n >= 4096
+        speculate = (PREFETCH_LADDER_INPUT and isinstance(src, _SawNode) and n >= 4096
                      and not L.pgx_stream_is_forked())
         if not speculate:
             ladder()
@@ -758,13 +789,11 @@ class _LadderNode(_Node):
             check(L.pgx_stream_select(0), "pgx_stream_select")
             ladder()
             check(L.pgx_stream_select(1), "pgx_stream_select")
-            saved = DeviceBuffer(src.state.shape, src.state.dtype)
-            check(L.pgx_memcpy_d2d(saved.ptr, src.state.ptr, saved.nbytes), "pgx_memcpy_d2d")
-            snapshot = (saved, src.last_end)
+            before = _StateBefore(src)
             nxt = src.render(start + n, n)                         # side stream, next to the ladder
         finally:
             check(L.pgx_stream_join(), "pgx_stream_join")          # what follows the ladder also follows the oscillators
-        self.ahead = (start + n, n, nxt, snapshot)
+        self.ahead = _Ahead(start + n, n, nxt, before)
         return out
 
 
@@ -816,11 +845,7 @@ class _CombNode(_Node):
 class _GateNode(_Node):
     def __init__(self, pes):
         super().__init__(pes, {})
-        rec = np.zeros(self.k, dtype=_dev.GATE_PARAMS)
-        for i, pe in enumerate(pes):
-            for key, v in pe._gate_params().items():
-                rec[i][key] = v
-        self.params = _dev.upload_structs(rec)
+        self.params = _dev.upload_structs(_param_records(_dev.GATE_PARAMS, pes, lambda pe: pe._gate_params()))
 
     def channels(self):
         return 1
@@ -837,20 +862,16 @@ class _AdsrGatedNode(_Node):
     def quiesce(self, keep=None):
         """keep = (start, n): the render that follows -- envelopes walked ahead for exactly that render stay (they were
         made from `state`, which they leave alone: a snapshot taken now is the state before them)."""
-        if keep is not None and self.ahead is not None and self.ahead[:2] == tuple(keep):
+        if keep is not None and self.ahead is not None and (self.ahead.start, self.ahead.n) == tuple(keep):
             return
         self.forget_ahead()
 
     def __init__(self, pes, children):
         super().__init__(pes, children)
-        rec = np.zeros(self.k, dtype=_dev.ADSR_PARAMS)
-        for i, pe in enumerate(pes):
-            for key, v in pe._adsr_params().items():
-                rec[i][key] = v
-        self.params = _dev.upload_structs(rec)
+        self.params = _dev.upload_structs(_param_records(_dev.ADSR_PARAMS, pes, lambda pe: pe._adsr_params()))
         self.state = DeviceBuffer((self.k, 3), np.float64, zero=True)
         self.ws = None
-        self.ahead = None            # (start, n, envelopes): render_ahead
+        self.ahead = None            # _Ahead(envelopes; nothing to undo): render_ahead
         self.state_next = None       # ... which reads `state` and leaves the states after the block here
         self.ring = []               # ... into one of three envelope buffers of its own, used in turn: [buffer, event]
         self.ring_at = 0             #     (event: recorded behind the mix that read the buffer last; None: never used)
@@ -887,11 +908,11 @@ class _AdsrGatedNode(_Node):
         if ahead is None:
             return None
         self.forget_ahead()
-        if ahead[0] == start and ahead[1] == n:
+        env = ahead.take(start, n)
+        if env is not None:
             self.state, self.state_next = self.state_next, self.state
             self.last = (start, n)
-            return ahead[2]
-        return None
+        return env
 
     def render_ahead(self, start, n, also=None, edges_here=False, behind_main=False) -> None:
         """Fused PeriodicGate only.  Edge search and walk go to the side stream, which starts behind what the main
@@ -924,7 +945,7 @@ class _AdsrGatedNode(_Node):
                 finally:
                     if L.pgx_stream_is_forked():
                         check(L.pgx_stream_detach(), "pgx_stream_detach")
-                self.ahead = (start, n, out)
+                self.ahead = _Ahead(start, n, out)
                 return
         else:
             if not self.ring or self.ring[0][0].shape != (self.k, n, 1):
@@ -943,7 +964,7 @@ class _AdsrGatedNode(_Node):
                   "pgx_adsr_gated_periodic_to")
         finally:
             check(L.pgx_stream_detach(), "pgx_stream_detach")
-        self.ahead = (start, n, out)
+        self.ahead = _Ahead(start, n, out)
 
     def mark_consumed(self, env) -> None:
         """Called behind the launch that read `env` (a buffer take_ahead handed out): from here on the main stream is done
@@ -1028,12 +1049,8 @@ def on_chip_mix_rule(pes) -> bool:
             return False
         chains.append((saw, pe))
     sr = float(pes[0].sample_rate)
-    rec = np.zeros(len(chains), dtype=_dev.BLITSAW_PARAMS)
-    for i, (saw, _) in enumerate(chains):
-        for key, v in saw._scalar_params().items():
-            rec[i][key] = v
-    if not (np.all(rec["m"] < 0.0) and np.all(rec["leak"] > 0.0) and np.all(rec["leak"] <= 0.9999)
-            and np.all(rec["freq"] >= 1.0) and wide_oscillators_ok(rec, sr)):        # (_BlitSawNode.closed_form_ok, .wide_ok)
+    rec = _param_records(_dev.BLITSAW_PARAMS, [saw for saw, _ in chains], lambda saw: saw._scalar_params())
+    if not (closed_form_ok(rec) and wide_oscillators_ok(rec, sr)):        # (what _BlitSawNode asks of its oscillators)
         return False
     for _, bq in chains:
         c = rbj_coefficients(bq._mode, bq._frequency, bq._q, bq._gain_db, sr)
@@ -1042,51 +1059,57 @@ def on_chip_mix_rule(pes) -> bool:
     return True
 
 
+class _Kind(NamedTuple):
+    """How one PE class is batched.  A voice tree is batchable when every PE of it is, and two trees are batched
+    together when their keys -- (tag, *extras, *children's keys) -- are equal."""
+    pe_class: type
+    tag: object                  # of the key: a string, or a function of the PE
+    batchable: object            # (pe) -> bool
+    extras: object               # (pe) -> what else goes into the key, or None
+    children: tuple              # ((name the node knows the child by, attribute of the PE that holds it, present(pe)), ...)
+    node: type                   # node(pes, children); node(pes) for a class without children
+
+
+_ALWAYS = lambda pe: True
+_SOURCE = ("source", "_source", _ALWAYS)
+_KINDS = (
+    _Kind(SinePE, "sine", lambda pe: not pe._has_pe_inputs(), lambda pe: (pe._channels,), (), _SineNode),
+    _Kind(BlitSawPE, "blitsaw", lambda pe: not pe.inputs(), lambda pe: (pe._channels,), (), _BlitSawNode),
+    _Kind(SuperSawPE, "supersaw", lambda pe: not pe.inputs(), lambda pe: (pe._channels, len(pe._oscillators)), (),
+          _SuperSawNode),
+    _Kind(BiquadPE, "biquad", lambda pe: not (pe._freq_is_pe or pe._q_is_pe), None, (_SOURCE,), _BiquadNode),
+    _Kind(LadderPE, "ladder", lambda pe: not (pe._freq_is_pe or pe._res_is_pe or pe._drive_is_pe), None, (_SOURCE,),
+          _LadderNode),
+    _Kind(CombPE, "comb", lambda pe: not (pe._freq_is_pe or pe._fb_is_pe), None, (_SOURCE,), _CombNode),
+    _Kind(PeriodicGate, "gate", lambda pe: pe.is_pure(), None, (), _GateNode),       # PE-driven gates carry a phase: not batched
+    _Kind(AdsrGatedPE, "adsr_gated", _ALWAYS, None, (("gate", "_gate", _ALWAYS),), _AdsrGatedNode),
+    _Kind(GainPE, lambda pe: "gain_pe" if pe._gain_is_pe else "gain", _ALWAYS, None,
+          (_SOURCE, ("gain", "_gain", lambda pe: pe._gain_is_pe)), _GainNode),
+)
+
+
+def _kind(pe):
+    for kind in _KINDS:
+        if isinstance(pe, kind.pe_class):
+            return kind
+    return None
+
+
 def _signature(pe):
     """Structural key of a voice tree, or None when the tree cannot be batched."""
     if pe.extent() != Extent(None, None):
         return None          # MixPE's extent-skip rule is per input; banks need always-on voices
-    if isinstance(pe, SinePE):
-        if pe._has_pe_inputs():
-            return None
-        return ("sine", pe._channels)
-    if isinstance(pe, BlitSawPE):
-        if pe.inputs():
-            return None
-        return ("blitsaw", pe._channels)
-    if isinstance(pe, SuperSawPE):
-        if pe.inputs():
-            return None
-        return ("supersaw", pe._channels, len(pe._oscillators))
-    if isinstance(pe, BiquadPE):
-        if pe._freq_is_pe or pe._q_is_pe:
-            return None
-        sub = _signature(pe._source)
-        return None if sub is None else ("biquad", sub)
-    if isinstance(pe, LadderPE):
-        if pe._freq_is_pe or pe._res_is_pe or pe._drive_is_pe:
-            return None
-        sub = _signature(pe._source)
-        return None if sub is None else ("ladder", sub)
-    if isinstance(pe, CombPE):
-        if pe._freq_is_pe or pe._fb_is_pe:
-            return None
-        sub = _signature(pe._source)
-        return None if sub is None else ("comb", sub)
-    if isinstance(pe, PeriodicGate):
-        return ("gate",) if pe.is_pure() else None        # PE-driven gates carry a phase: not batched
-    if isinstance(pe, AdsrGatedPE):
-        sub = _signature(pe._gate)
-        return None if sub is None else ("adsr_gated", sub)
-    if isinstance(pe, GainPE):
-        sub = _signature(pe._source)
-        if sub is None:
-            return None
-        if pe._gain_is_pe:
-            g = _signature(pe._gain)
-            return None if g is None else ("gain_pe", sub, g)
-        return ("gain", sub)
-    return None
+    kind = _kind(pe)
+    if kind is None or not kind.batchable(pe):
+        return None
+    key = (kind.tag(pe) if callable(kind.tag) else kind.tag,) + (kind.extras(pe) if kind.extras else ())
+    for _, attribute, present in kind.children:
+        if present(pe):
+            sub = _signature(getattr(pe, attribute))
+            if sub is None:
+                return None
+            key += (sub,)
+    return key
 
 
 def _collect_ids(pe, seen):
@@ -1097,47 +1120,27 @@ def _collect_ids(pe, seen):
 
 
 def _build(pes):
-    pe = pes[0]
-    if isinstance(pe, SinePE):
-        return _SineNode(pes)
-    if isinstance(pe, BlitSawPE):
-        return _BlitSawNode(pes)
-    if isinstance(pe, SuperSawPE):
-        return _SuperSawNode(pes)
-    if isinstance(pe, BiquadPE):
-        return _BiquadNode(pes, {"source": _build([p._source for p in pes])})
-    if isinstance(pe, LadderPE):
-        return _LadderNode(pes, {"source": _build([p._source for p in pes])})
-    if isinstance(pe, CombPE):
-        return _CombNode(pes, {"source": _build([p._source for p in pes])})
-    if isinstance(pe, PeriodicGate):
-        return _GateNode(pes)
-    if isinstance(pe, AdsrGatedPE):
-        return _AdsrGatedNode(pes, {"gate": _build([p._gate for p in pes])})
-    if isinstance(pe, GainPE):
-        children = {"source": _build([p._source for p in pes])}
-        if pe._gain_is_pe:
-            children["gain"] = _build([p._gain for p in pes])
-        return _GainNode(pes, children)
-    raise TypeError(type(pe).__name__)
+    kind = _kind(pes[0])
+    if kind is None:
+        raise TypeError(type(pes[0]).__name__)
+    if not kind.children:
+        return kind.node(pes)
+    return kind.node(pes, {name: _build([getattr(p, attribute) for p in pes])
+                           for name, attribute, present in kind.children if present(pes[0])})
 
 
-class VoiceBank:
+class VoiceBank(_Windowed):
     def __init__(self, inputs):
         self.k = len(inputs)
         self.root = _build(list(inputs))
         if isinstance(self.root, _LadderNode):
             self.root.is_root = True
         self.mix_windows = False     # windows at the level of the mix whatever the root (set_mix_windows)
-        self.win = None              # [first, end, n, mixed window (Snippet), served, [(node, snapshot)]]
-        self.last = None             # (start, n) of the last block handed out
+        self._reset_windows(BANK_WINDOW_FIRST)       # win.buf: the mixed window (Snippet), win.undo: [(node, snapshot)]
         self.streaming = False       # the block being rendered continues the one before it, same length
-        self.grow = BANK_WINDOW_FIRST
 
     def reset(self) -> None:
-        self.win = None
-        self.last = None
-        self.grow = BANK_WINDOW_FIRST
+        self._reset_windows(BANK_WINDOW_FIRST)
         self.root.reset()
 
     def set_mix_windows(self) -> None:
@@ -1163,12 +1166,10 @@ class VoiceBank:
         return found
 
     def _settle_window(self) -> None:
-        win, self.win = self.win, None
-        if win is None:
+        left = self._close_window()
+        if left is None:
             return
-        first, end, n, big, served, snaps = win
-        if served >= end:
-            return                                       # consumed to the last frame: the states are already there
+        first, served, snaps = left
         for node in self._nodes():
             node.quiesce()
         for node, snap in snaps:
@@ -1177,17 +1178,15 @@ class VoiceBank:
             self._render_mix_now(first, served - first)
 
     def render_mix(self, start: int, duration: int) -> Snippet:
-        win = self.win
-        if win is not None:
-            if start == win[4] and duration == win[2] and start + duration <= win[1]:
-                win[4] = start + duration
-                self.last = (start, duration)
-                row = Snippet.window_rows(start, win[3].dev, start - win[0], duration)
-                row._bank_window = True
-                return row
+        offset = self._next_row(start, duration)
+        if offset is not None:
+            row = Snippet.window_rows(start, self.win.buf.dev, offset, duration)
+            row._bank_window = True
+            return row
+        closed = self.win          # (held to the end of this pull: its buffers return to the pool behind what is enqueued here)
+        if closed is not None:
             self._settle_window()
-        streaming = self.streaming = self.last == (start - duration, duration)
-        self.last = (start, duration)
+        streaming = self.streaming = self._continues(start, duration)
         # (SuperSaw banks below the size that fills the chip: measured 44 -> 23 us per block for a rank's 64 instances,
         # 62 -> 42 for 128.  Not 256 and more -- rendered one block ahead already, a window ahead is too much thrown away
         # when the stream ends: 97 -> 155 us; not the C5 graph -- its envelope walk and mixes do not shrink with the
@@ -1200,18 +1199,15 @@ class VoiceBank:
             # (a ladder root -- a rank's share of C4 -- takes the ladder bank's longer windows: its lanes' warm-up does
             # not shrink with the share, so the fewer instances a rank owns the more of a short window is warm-up)
             ladder_root = isinstance(self.root, _LadderNode)
-            blocks = max(1, min(self.grow, (LADDER_WINDOW_FRAMES if ladder_root else BANK_WINDOW_FRAMES) // duration))
+            blocks = self._window_blocks(duration, LADDER_WINDOW_MAX if ladder_root else BANK_WINDOW_MAX,
+                                         LADDER_WINDOW_FRAMES if ladder_root else BANK_WINDOW_FRAMES)
             if blocks > 1:
-                self.grow = min(self.grow * 2, LADDER_WINDOW_MAX if ladder_root else BANK_WINDOW_MAX)
                 nodes = self._nodes()
                 for node in nodes:
                     node.quiesce(keep=(start, duration * blocks))
                 snaps = [(node, node.snapshot()) for node in nodes if node._STATE]
                 big = self._render_mix_now(start, duration * blocks)
-                from . import look_ahead as _look_ahead
-                _look_ahead.STATS["window_frames"] += duration * blocks
-                _look_ahead.STATS["windows"] += 1
-                self.win = [start, start + duration * blocks, duration, big, start + duration, snaps]
+                self._open_window(start, blocks, duration, big, snaps)
                 row = Snippet.window_rows(start, big.dev, 0, duration)
                 row._bank_window = True
                 return row
@@ -1259,8 +1255,7 @@ class VoiceBank:
         # (the voices-summed-on-chip bank + mix stay on one stream: with the bank one block ahead and the mix on the
         # side stream a rank's share went from 60.5 to 64.3 us -- the fork / join packets cost more than the 5 us mix)
         if (PREFETCH_SUPERSAW_VOICES and isinstance(root, _SuperSawNode) and duration >= 4096
-                and (PIPELINE_FULL_SUPERSAW_BANK if root.fused()
-                     else (PIPELINE_SUPERSAW_BANK or not root.banked(duration)))
+                and (PIPELINE_FULL_SUPERSAW_BANK if root.fused() else not root.banked(duration))
                 and not lib().pgx_stream_is_forked()):
             return self._supersaw_pipelined(start, duration)
         if isinstance(root, _BiquadNode) and root.mixes_on_chip(duration):
@@ -1301,52 +1296,25 @@ class VoiceBank:
                 ahead_ok = ENVELOPE_AHEAD and duration >= 1024 and not L.pgx_stream_is_forked()
                 streaming = gain.last == (start - duration, duration)      # equal blocks, one after the other
                 source = root.children["source"]
-                gained = False
                 if ahead_ok and gain.ahead is not None:
                     # this block's envelopes were walked while the last block was mixed (the wait for the side stream is
-                    # no wait by now).  A chain that takes the gain can multiply by them in its own kernel -- the mix then
-                    # reads one [voices][frames] layer, not two (35 -> 17 us) -- but the oscillators then depend on the
-                    # envelopes, the next walk has to start in front of them and shares their SIMDs from the first tile:
-                    # 512 voices 139 us per block against 137, 256 voices 91 against 90.  Off.
-                    if FUSE_GAIN_IN_CHAIN and isinstance(source, _BiquadNode) and source.takes_gain():
-                        g = gain.take_ahead(start, duration)
-                        if g is not None:
-                            # (the next block's walk first: the oscillators now depend on this block's envelopes, so a
-                            # walk that starts behind them would be finished only a whole walk after them)
-                            if streaming:
-                                gain.render_ahead(start + duration, duration)
-                                streaming = False
-                            x = source.render(start, duration, gain=g)
-                            gained = True
-                        else:                           # a seek: walked now, beside the oscillators
-                            try:
-                                g = gain.render(start, duration, detach=True)
-                                x = source.render(start, duration)
-                            finally:
-                                if L.pgx_stream_is_forked():
-                                    check(L.pgx_stream_join(), "pgx_stream_join")
-                    else:
-                        x = source.render(start, duration)
-                        g = gain.take_ahead(start, duration)
-                        if g is None:                   # a seek: walked now, behind the oscillators
-                            g = gain.render(start, duration)
+                    # no wait by now).  (Multiplying by them in the chain's own kernel -- the mix then reads one
+                    # [voices][frames] layer, not two: 35 -> 17 us -- made the oscillators depend on the envelopes; the next
+                    # walk had to start in front of them and shared their SIMDs from the first tile: 512 voices 139 us per
+                    # block against 137, 256 voices 91 against 90.  Removed.)
+                    x = source.render(start, duration)
+                    g = gain.take_ahead(start, duration)
+                    if g is None:                       # a seek: walked now, behind the oscillators
+                        g = gain.render(start, duration)
                 else:
                     # edge search first (parallel, short), then the walk detached on the side stream
                     try:
                         g = gain.render(start, duration, detach=True)
-                        x = root.children["source"].render(start, duration)
+                        x = source.render(start, duration)
                     finally:
                         if L.pgx_stream_is_forked():        # the fork happens inside the detached render
                             check(L.pgx_stream_join(), "pgx_stream_join")
                 walk_ahead = ahead_ok and streaming
-                if gained:
-                    if walk_ahead:
-                        gain.render_ahead(start + duration, duration)
-                    ch = x.shape[2]
-                    out = DeviceBuffer((duration, ch), np.float32)
-                    check(L.pgx_mix_batch(out.ptr, x.ptr, duration * ch, self.k, duration * ch), "pgx_mix_batch")
-                    gain.mark_consumed(g)                   # (read by the chain kernel, which is behind us too)
-                    return Snippet(start, out)
             else:
                 check(L.pgx_stream_fork(), "pgx_stream_fork")
                 try:
