@@ -964,6 +964,52 @@ int pgx_restart_gather(float *out, int64_t n, int channels, const float *trigger
                        const void *workspace, int64_t carry_local, const int32_t *sel_dev, int64_t n_sel,
                        const pgx_restart_take *takes_dev, int n_takes);
 
+/* ------------------------------------------------------------------ ReversePitchEchoPE (pgx_reverse_echo.hip)
+ * ReversePitchEchoPE._render through _reverse_pitch_echo_numba (reverse_pitch_echo_pe.py:30-265): the block-size
+ * one-pole, the two-head pitch shifter and the double-buffered reversed echo.  float32 in (n frames of `channels`
+ * interleaved), float32 out (the windowed playback alone), float64 inside.  Each of block_seconds / pitch_ratio /
+ * feedback / alternate is the scalar, or a float32 (n, 1) stream that overrides it (widened to float64 on load).
+ *
+ * Everything carried from one render to the next lives on the device: the record below, the two echo buffers
+ * (rows * channels float64 each, row-major; rows = max(65, int(10 * sample_rate))) and the pitch history
+ * (2 * pitch_len * channels float64; pitch_len = max(2, int(sample_rate / 60))).  The pitch history is the reference's
+ * circular buffer in time order: row j of half `pitch_parity` is the input pitch_len - j frames before the next one;
+ * each render writes the other half.  A new stream starts from zeroed buffers and a record of {smoothed = the
+ * clamped, rounded initial size, current_is_a = 1, reverse = 1, everything else 0}.
+ *
+ * Three launches: a one-workgroup plan (float64 scans of the smoothed size and of the read position, re-associated;
+ * one lane walks the echo-block boundaries, one step per echo block of >= PGX_REVERSE_ECHO_MIN_BLOCK frames), a
+ * grid-wide pitch stage and an echo stage of one workgroup per channel; no workgroup reads what another wrote in the
+ * same launch.  A pitch ratio is taken as >= PGX_REVERSE_ECHO_MIN_RATIO (NaN too) and is expected to stay below
+ * pitch_len, where the reference's read position stays inside its buffer.
+ * workspace: pgx_reverse_echo_workspace_bytes(n, channels) bytes of device scratch (0 for n < 1).
+ * PGX_ERR_INVALID, whether or not the library is initialised: a null state / buffer pointer (out / in / workspace may
+ * be null for n == 0 only), channels < 1, n < 0, rows <= PGX_REVERSE_ECHO_MIN_BLOCK, pitch_len < 2,
+ * smoothing_samples < 1, a sample rate that is not positive.  n == 0: success, nothing is launched. */
+#define PGX_REVERSE_ECHO_MIN_BLOCK 64
+#define PGX_REVERSE_ECHO_MAX_FEEDBACK 0.995
+#define PGX_REVERSE_ECHO_MIN_RATIO 0.001
+#define PGX_REVERSE_ECHO_UNITY_BAND 1e-4
+typedef struct {
+    double smoothed;          /* _smoothed_block_samples */
+    double read_pos;          /* _pitch_read_pos, in [0, pitch_len) */
+    int64_t write_idx;        /* _write_idx */
+    int64_t read_idx;         /* _read_idx: moves with write_idx */
+    int64_t current_block;    /* _current_block_samples: locked at write_idx == 0 */
+    int64_t prev_len;         /* _previous_block_samples */
+    int64_t pitch_write_pos;  /* _pitch_write_pos */
+    int32_t reverse;          /* _playback_reverse */
+    int32_t current_is_a;     /* _current_is_a */
+    int32_t pitch_parity;     /* the half of the pitch history the next render reads */
+    int32_t pad;
+} pgx_reverse_echo_state;
+size_t pgx_reverse_echo_workspace_bytes(int64_t n, int channels);
+int pgx_reverse_echo(float *out, const float *in, int64_t n, int channels, double sample_rate, double block_seconds,
+                     const float *block_stream, double pitch_ratio, const float *pitch_stream, double feedback,
+                     const float *feedback_stream, double alternate, const float *alternate_stream,
+                     int64_t smoothing_samples, pgx_reverse_echo_state *state, double *echo_a, double *echo_b,
+                     int64_t rows, double *pitch_history, int64_t pitch_len, void *workspace);
+
 #ifdef __cplusplus
 }
 #endif

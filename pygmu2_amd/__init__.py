@@ -7,7 +7,8 @@ SinePE, BlitSawPE, SuperSawPE, BiquadPE, LadderPE, CombPE, MixPE, GainPE, Convol
 AdsrGatedPE, AdsrTriggeredPE, PeriodicGate, PeriodicTrigger, ConstantPE, ArrayPE,
 DiracPE, IdentityPE, CachePE, CropPE, SVFilterPE, EnvelopePE, TransformPE, DelayPE, PiecewisePE,
 TriggerRestartPE, ReverbPE, WavWriterPE, WavReaderPE, KarplusStrongPE, AnalogOscPE, WavetablePE, TimeWarpPE,
-SampleHoldPE, TrackHoldPE, SlewLimiterPE, FunctionGenPE, NoisePE, TralfamPE, SlicePE, SetExtentPE, SequencePE
+SampleHoldPE, TrackHoldPE, SlewLimiterPE, FunctionGenPE, NoisePE, TralfamPE, SlicePE, SetExtentPE, SequencePE,
+ReversePitchEchoPE
 (+ render_to_file, rho_for_decay_db, pitch_to_freq and the other unit conversions).  Snippet payloads live in HBM; all DSP runs in
 hand-written HIP kernels for gfx950 behind the C ABI of include/pygmu_hip.h.
 """
@@ -98,6 +99,10 @@ from .temperament import (CustomTemperament, EqualTemperament, JustIntonation, P
 # under oracle/ for every name listed there; tests/test_gpu_random_select.py holds it to fixtures of the reference.
 from . import restart_bank
 from .random_select_pe import RandomSelectPE
+# ReversePitchEchoPE: the same arrangement (pg.ReversePitchEchoPE works, it is not in __all__): the fuzz census of
+# tests/test_oracle_fuzz_golden.py needs an evaluator under oracle/ for every name listed there;
+# tests/test_gpu_reverse_echo.py holds it to fixtures of the reference.
+from .reverse_pitch_echo_pe import ReversePitchEchoPE
 from .utils import render_to_file
 from . import device, diagnostics
 

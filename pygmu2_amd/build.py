@@ -38,6 +38,7 @@ SOURCES = [
     "pgx_score.hip",
     "pgx_tuning.hip",
     "pgx_restart.hip",
+    "pgx_reverse_echo.hip",
 ]
 
 # -ffp-contract=off: the parity contract is "same float64 operation order as the reference's

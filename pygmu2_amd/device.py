@@ -195,6 +195,8 @@ _SIGNATURES = [
     ("pgx_score_mix", _I, [_P, _L, _I, _P, _L, _P, _P, _L]),
     ("pgx_restart_plan", _I, [_P, _P, _P, _I, _L]),
     ("pgx_restart_gather", _I, [_P, _L, _I, _P, _I, _P, _L, _P, _L, _P, _I]),
+    ("pgx_reverse_echo_workspace_bytes", _Z, [_L, _I]),
+    ("pgx_reverse_echo", _I, [_P, _P, _L, _I, _D, _D, _P, _D, _P, _D, _P, _D, _P, _L, _P, _P, _P, _L, _P, _L, _P]),
 ]
 
 EXPORTED_SYMBOLS = [s[0] for s in _SIGNATURES]
@@ -229,6 +231,13 @@ RESTART_TILE = 2048                 # PGX_RESTART_TILE: frames per tile of pgx_r
 RESTART_MAX_SEGMENTS = 1024         # PGX_RESTART_MAX_SEGMENTS: workgroups per launch at most
 RESTART_WORKSPACE_INT64 = 4 * RESTART_MAX_SEGMENTS
 RESTART_TAKE = np.dtype([("ptr", "<u8"), ("first", "<i8"), ("len", "<i8")])
+REVERSE_ECHO_MIN_BLOCK = 64         # PGX_REVERSE_ECHO_MIN_BLOCK: frames of the shortest echo block
+REVERSE_ECHO_MAX_FEEDBACK = 0.995   # PGX_REVERSE_ECHO_MAX_FEEDBACK
+REVERSE_ECHO_MIN_RATIO = 0.001      # PGX_REVERSE_ECHO_MIN_RATIO
+REVERSE_ECHO_UNITY_BAND = 1e-4      # PGX_REVERSE_ECHO_UNITY_BAND: |ratio - 1| below it bypasses the pitch shifter
+REVERSE_ECHO_STATE = np.dtype([("smoothed", "<f8"), ("read_pos", "<f8"), ("write_idx", "<i8"), ("read_idx", "<i8"),
+                               ("current_block", "<i8"), ("prev_len", "<i8"), ("pitch_write_pos", "<i8"),
+                               ("reverse", "<i4"), ("current_is_a", "<i4"), ("pitch_parity", "<i4"), ("pad", "<i4")])
 NOISE_PARAMS = np.dtype([("state_hi", "<u8"), ("state_lo", "<u8"), ("inc_hi", "<u8"), ("inc_lo", "<u8"),
                          ("consumed", "<i8"), ("scaled", "<i4"), ("span", "<f4"), ("min_value", "<f4"), ("pad", "<i4")])
 NOISE_STATE = np.dtype([("pink", "<f4", (7,)), ("brown", "<f4")])
