@@ -220,6 +220,12 @@ int pgx_biquad_sine(float *out, int64_t start, int64_t n, double sample_rate, do
  * the wave runs off (environment: PGX_SB_SINE_RUNS), a negative value restores the default.  Returns the previous
  * value.  pgx_biquad_sine_supported answers the same either way. */
 int pgx_biquad_sine_set_runs(int min_chunks);
+/* The wave-run plan pgx_biquad_sine would render a block of n frames by, in 1024-frame chunks: out = {run, head, tail,
+ * warm, waves}.  Wave 0 renders the chunks [0, head) and the last `tail` ones, wave g >= 1 the `run` chunks from
+ * head + (g - 1) * run, each after `warm` chunks of warm-up.  Returns 1, or 0 (out untouched) when the single-launch
+ * filter kernel would render the block; follows pgx_biquad_sine_set_runs.  Needs pgx_init (the plan is sized by the
+ * device's resident waves). */
+int pgx_biquad_sine_runs_plan(int64_t n, int64_t settle_frames, int out[5]);
 
 /* Time-varying coefficients: _compute_coefficients per sample (biquad_pe.py:217-335) +
  * the direct-form-I recurrence of _biquad_varying_numba (biquad_pe.py:35-62).

@@ -987,12 +987,56 @@ __device__ __forceinline__ double readlane63_f64(double v) {
     return __hiloint2double(hi, lo);
 }
 
+// Experiment switches of the window kernel (PGX_EXTRA_FLAGS; tools/c2_window_phases.py builds and times them):
+//   PGX_SB_RUNS_NO_STORE  the hot path's global stores compiled out: wrong output, the timing of everything else
+//   PGX_SB_RUNS_STAMPS    every wave records wall_clock64() (100 MHz) at entry, with its constants ready, after its
+//                         first stored chunk and at exit (pgx_biquad_sine_runs_stamps reads them)
+typedef unsigned int runs_v4u __attribute__((ext_vector_type(4)));
+
+// stage_store for the runs kernel's full, aligned chunks: 16 consecutive frames per lane -> four coalesced 1 KB rows,
+// stored write-through (sc1).  A plain store leaves its line dirty in the XCD's L2, and a kernel that ends with up to
+// 32 MiB of dirty lines pays for their write-back at the boundary to the next launch: 3.5 us from the last wave's exit
+// to the next window's first entry, 1.2 us with write-through.  A run is 4 KB x `run` chunks, a block
+// 12.6 M frames and more -- far beyond the 32 MiB of L2 -- so no reader of these lines is served from L2 today and
+// nothing is lost when the store drops them.  The buffer resource is based at the chunk (the same address in every
+// lane), so every offset is below 4 KB whatever the size of the window.
+__device__ __forceinline__ void runs_store_chunk(float *lds, float *dst, int lane, const float (&y)[kBqT]) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+        *reinterpret_cast<float4 *>(lds + lane * 20 + 4 * i) = make_float4(y[4 * i], y[4 * i + 1], y[4 * i + 2], y[4 * i + 3]);
+    const uint64_t p = (uint64_t)dst;
+    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)p), hi = __builtin_amdgcn_readfirstlane((uint32_t)(p >> 32));
+    __amdgpu_buffer_rsrc_t rsrc =
+        __builtin_amdgcn_make_buffer_rsrc((void *)(((uint64_t)hi << 32) | lo), 0, kRunChunk * 4, 0x00020000);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const runs_v4u r = *reinterpret_cast<const runs_v4u *>(lds + stage_slot(i, lane));
+#ifdef PGX_SB_RUNS_NO_STORE
+        asm volatile("" ::"v"(r));
+#else
+        __builtin_amdgcn_raw_buffer_store_b128(r, rsrc, lane * 16, i * 1024, 16 /* sc1 */);
+#endif
+    }
+}
+
+#ifdef PGX_SB_RUNS_STAMPS
+constexpr int kRunStampWaves = 4096;
+__device__ unsigned long long g_runs_stamps[2][kRunStampWaves][4];
+#endif
+
 __global__ void __launch_bounds__(kRunBlock, PGX_SB_RUNS_WAVES)
 k_biquad_sine_runs(float *__restrict__ out, int64_t n, const double *__restrict__ coef,
                    const double *__restrict__ tables, double *state, int run, int head, int tail, int warm, int waves,
-                   SbRuns sine) {
+                   SbRuns sine
+#ifdef PGX_SB_RUNS_STAMPS
+                   , int stamp_slot
+#endif
+                   ) {
     __shared__ __attribute__((aligned(16))) float stage_lds[(kRunBlock / 64) * kStageWords];
     __shared__ __attribute__((aligned(16))) double rows_lds[2 * kBqT];
+#ifdef PGX_SB_RUNS_STAMPS
+    unsigned long long stamp[4] = {(unsigned long long)wall_clock64(), 0, 0, 0};
+#endif
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const double *tb = tables;
     // the first rows of A^j (pass 2), read as LDS broadcasts (see k_biquad_settled): the kernel's only barrier
@@ -1015,6 +1059,10 @@ k_biquad_sine_runs(float *__restrict__ out, int64_t n, const double *__restrict_
     const M2 mlane = load_m2(tb + 28 + 4 * lane);
     const M2 m16 = load_m2(tb + 28 + 4 * ((lane & 15) + 1));
     const M2 m32 = load_m2(tb + 28 + 4 * ((lane & 31) + 1));
+#ifdef PGX_SB_RUNS_STAMPS
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::"v"(mlane.a), "v"(m16.a), "v"(m32.a), "v"(pwave.a), "v"(b0) : "memory");
+    stamp[1] = wall_clock64();
+#endif
 
     // renders the chunks [cb, ce) after `warm` chunks of warm-up (from the carried state at chunk 0).  Called once per
     // range, not from a loop over the ranges: the sine's constants are then not hoisted into registers for all of it
@@ -1069,9 +1117,15 @@ k_biquad_sine_runs(float *__restrict__ out, int64_t n, const double *__restrict_
                 for (int j = 0; j < kBqT; ++j)
                     yf[j] = (float)__builtin_fma(rows[2 * j], zin.x, __builtin_fma(rows[2 * j + 1], zin.y, yz[j]));
                 if (PGX_HOT(io_aligned && w0 + kRunChunk <= n))
-                    stage_store(wlds, out + w0, lane, yf);
+                    runs_store_chunk(wlds, out + w0, lane, yf);
                 else
                     store_frames<kBqT>(out, f0, n, 1, 0, yf);
+#ifdef PGX_SB_RUNS_STAMPS
+                if (!stamp[2]) {
+                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                    stamp[2] = wall_clock64();
+                }
+#endif
                 if (PGX_COLD(f0 <= n - 1 && n - 1 - f0 < kBqT)) {  // the lane holding the last frame: new state
                     // its frames made again (bit for bit the same), rather than kept in 16 registers for this branch
                     double rs = sn, rc = cs;
@@ -1104,6 +1158,12 @@ k_biquad_sine_runs(float *__restrict__ out, int64_t n, const double *__restrict_
         const int64_t cb = head + (int64_t)(g - 1) * run;
         render(cb, cb + run < tail_start ? cb + run : tail_start);
     }
+#ifdef PGX_SB_RUNS_STAMPS
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    stamp[3] = wall_clock64();
+    if (lane == 0 && g < kRunStampWaves)
+        for (int k = 0; k < 4; ++k) g_runs_stamps[stamp_slot & 1][g][k] = stamp[k];
+#endif
 }
 
 struct BqPlan {
@@ -4299,6 +4359,30 @@ int pgx_biquad_sine_set_runs(int min_chunks) {
     return was;
 }
 
+int pgx_biquad_sine_runs_plan(int64_t n, int64_t settle_frames, int out[5]) {
+    if (!out || n <= 0 || !pgx::initialised()) return 0;
+    const RunsPlan rp = biquad_sine_runs_plan(n, settle_frames);
+    if (!rp.ok || !biquad_sine_plan(n, settle_frames).ok) return 0;
+    out[0] = rp.run;
+    out[1] = rp.head;
+    out[2] = rp.tail;
+    out[3] = rp.warm;
+    out[4] = rp.waves;
+    return 1;
+}
+
+#ifdef PGX_SB_RUNS_STAMPS
+static int g_runs_stamp_launch = 0;
+// the stamps of the last two window launches, [2][4096][4] ticks of 10 ns; slot = launch number & 1.  Returns the
+// number of launches so far (after a device synchronise).
+extern "C" int pgx_biquad_sine_runs_stamps(unsigned long long *host_out) {
+    if (hipDeviceSynchronize() != hipSuccess ||
+        hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_runs_stamps), sizeof(unsigned long long) * 2 * kRunStampWaves * 4) != hipSuccess)
+        return -1;
+    return g_runs_stamp_launch;
+}
+#endif
+
 int pgx_biquad_sine(float *out, int64_t start, int64_t n, double sample_rate, double w, double amp, double phase0,
                     const double *coef, const double *tables, int64_t settle_frames, double *state,
                     double *state_backup) {
@@ -4360,8 +4444,13 @@ int pgx_biquad_sine(float *out, int64_t start, int64_t n, double sample_rate, do
         sine.start = start;
         sine.state_backup = state_backup;
         const int groups = (rp.waves + kRunBlock / 64 - 1) / (kRunBlock / 64);
+#ifdef PGX_SB_RUNS_STAMPS
+        hipLaunchKernelGGL(k_biquad_sine_runs, dim3(groups), dim3(kRunBlock), 0, pgx::stream(), out, n, coef, tables,
+                           state, rp.run, rp.head, rp.tail, rp.warm, rp.waves, sine, g_runs_stamp_launch++);
+#else
         hipLaunchKernelGGL(k_biquad_sine_runs, dim3(groups), dim3(kRunBlock), 0, pgx::stream(), out, n, coef, tables,
                            state, rp.run, rp.head, rp.tail, rp.warm, rp.waves, sine);
+#endif
         PGX_LAUNCH_CHECK("k_biquad_sine_runs");
         return PGX_OK;
     }

@@ -5,7 +5,11 @@ problem sizes (e.g. the 1M-frame and the 2^26-frame biquad launches of bench.py)
 stock --stats summary averages together.
 
     python tools/summarize_trace.py gpurun_out/prof/<pid>_kernel_trace.csv > profiles/<name>.md
-"""
+    python tools/summarize_trace.py <csv> --intervals k_biquad_sine_runs     # start-to-start of consecutive launches
+
+--intervals: for the launches of one kernel (substring of its name) at its most frequent grid, the time from one
+launch's start to the next one's, where no other kernel ran in between -- a kernel's duration leaves out whatever the
+boundary between two dependent launches costs (dispatch, the write-back of dirty cache lines)."""
 
 import csv
 import re
@@ -38,5 +42,40 @@ def main(path):
               f"{vg} | {ag} | {sg} | {lds} |")
 
 
+def intervals(path, match):
+    rows = []
+    with open(path) as f:
+        for row in csv.DictReader(f):
+            rows.append((int(row["Start_Timestamp"]), int(row["End_Timestamp"]), short(row["Kernel_Name"]),
+                         int(row["Grid_Size_X"])))
+    rows.sort()
+    grids = defaultdict(int)
+    for _, _, name, gx in rows:
+        if match in name:
+            grids[gx] += 1
+    if not grids:
+        print(f"no launch of a kernel matching {match}")
+        return
+    grid = max(grids, key=grids.get)
+    s2s, dur, gap = [], [], []
+    for a, b in zip(rows, rows[1:]):
+        if match in a[2] and match in b[2] and a[3] == grid and b[3] == grid:
+            s2s.append(b[0] - a[0])
+            dur.append(a[1] - a[0])
+            gap.append(b[0] - a[1])
+    if not s2s:
+        print(f"no two consecutive launches of {match} at grid {grid}")
+        return
+    # the stream's launches follow each other at once only while the host keeps up: the shorter half is the device's pace
+    med = lambda v: sorted(v)[len(v) // 2] / 1e3
+    print("| kernel | grid (threads) | pairs | start-to-start us: median | min | duration us: median | end-to-start us: median | min |")
+    print("|---|---|---|---|---|---|---|---|")
+    print(f"| {match} | {grid} | {len(s2s)} | {med(s2s):.2f} | {min(s2s) / 1e3:.2f} | {med(dur):.2f} | {med(gap):.2f} | "
+          f"{min(gap) / 1e3:.2f} |")
+
+
 if __name__ == "__main__":
-    main(sys.argv[1])
+    if len(sys.argv) >= 4 and sys.argv[2] == "--intervals":
+        intervals(sys.argv[1], sys.argv[3])
+    else:
+        main(sys.argv[1])
