@@ -285,6 +285,11 @@ typedef struct {
     double p1;
 } pgx_transform_op;
 int pgx_transform(float *out, const float *in, int64_t n_elems, const pgx_transform_op *ops, int nops);
+/* A bank of `batch` such chains with the same steps and per-voice parameters (voice_bank.py): voice i runs
+ * ops[i * nops .. (i + 1) * nops) over the per_voice elements at in + i * per_voice -- the same arithmetic, one launch
+ * (the voice is blockIdx.y; batch <= 65535). */
+int pgx_transform_bank(float *out, const float *in, int64_t per_voice, int batch, const pgx_transform_op *ops,
+                       int nops);
 
 /* TransformPE chains that hold a tuning step (pygmu2_amd/transforms.py: PitchToFreq, FreqToPitch, SemitonesToRatio,
  * RatioToSemitones over temperament.py's EqualTemperament / JustIntonation): float32 -> float64 -> ops in order ->
@@ -859,6 +864,26 @@ int pgx_analog_osc_pure(float *out, int64_t start, int64_t n, int channels, doub
 int pgx_analog_osc_stateful(float *out, int64_t n, int channels, double sample_rate, int waveform, double freq,
                             double duty, const float *freq_stream, const float *duty_stream, int restart,
                             double *state /* [2] */, void *workspace);
+
+/* A bank of `batch` AnalogOscPEs of one waveform and channel count (voice_bank.py): the same kernels with the voice in
+ * blockIdx.y (the single entry points above are batch = 1), so a bank takes as many launches as one PE -- 1 (pure
+ * rectangle), 3 (pure sawtooth, stateful rectangle), 5 (stateful sawtooth) -- and voice i gets, operation for
+ * operation, the samples of pgx_analog_osc_pure / pgx_analog_osc_stateful for that voice alone.  Voice i writes n
+ * frames at out + i * out_stride, reads params[i] (device memory), its (n, 1) streams at freq_streams + i * freq_stride
+ * / duty_streams + i * duty_stride (NULL: the scalar of params[i]), carries state[i] and scans in its own
+ * pgx_analog_osc_workspace_bytes(n) slice of `workspace`.  stateful == 0: the pure form -- both streams must be NULL,
+ * `state` is unused, `start` is the first frame's index; the rectangle needs no workspace.  stateful != 0: the carried
+ * form (`start` is unused), restart as above for every voice.  batch <= 65535. */
+typedef struct {
+    double freq;
+    double duty;
+} pgx_osc_params;
+size_t pgx_analog_osc_bank_workspace_bytes(int64_t n, int batch);
+int pgx_analog_osc_bank(float *out, int64_t out_stride, int batch, int64_t start, int64_t n, int channels,
+                        double sample_rate, int waveform, const pgx_osc_params *params /* [batch] */,
+                        const float *freq_streams, int64_t freq_stride, const float *duty_streams,
+                        int64_t duty_stride, int stateful, int restart, double *state /* [batch][2] */,
+                        void *workspace);
 
 /* ------------------------------------------------------------------ NoisePE (pgx_noise.hip)
  * NoisePE._render (noise_pe.py:111-165): np.random.default_rng(seed).uniform(-1, 1, n).astype(float32) drawn on the

@@ -15,7 +15,9 @@
 // index (one element-wise launch).  The sawtooth integrates its derivative and the stateful form integrates the phase
 // increment: those go through a three-pass float64 scan (per-workgroup sums, one workgroup scanning the sums with the
 // carried state, per-workgroup re-evaluation), twice for the stateful sawtooth.  The carried phase / saw value live in
-// a device state blob; nothing here synchronises.
+// a device state blob; nothing here synchronises.  A bank of oscillators (pgx_analog_osc_bank, voice_bank.py) is the same
+// kernels with the voice as a grid dimension -- blockIdx.y of a pass, a scan workgroup per voice -- on per-voice parameters,
+// streams, state and workspace slice: the launches of one PE, each voice's samples bit for bit.
 
 #include "pgx_common.h"
 
@@ -317,7 +319,22 @@ struct OscArgs {
     int64_t start, n;
     int channels;
     const float *freq, *duty;     // stateful: float32 streams or NULL (scalar)
+    // a bank: the voice is blockIdx.y of a pass (blockIdx.x of a scan); voice v writes at out + v * out_stride, reads
+    // params[v] (NULL: p.freq / p.duty, the single PE) and its streams at + v * stride
+    const pgx_osc_params *params;
+    int64_t out_stride, freq_stride, duty_stride;
 };
+
+// What voice v sees: its scalars, its streams.
+__device__ __forceinline__ OscArgs osc_voice(OscArgs a, int v) {
+    if (a.params) {
+        a.p.freq = a.params[v].freq;
+        a.p.duty = a.params[v].duty;
+    }
+    if (a.freq) a.freq += (int64_t)v * a.freq_stride;
+    if (a.duty) a.duty += (int64_t)v * a.duty_stride;
+    return a;
+}
 
 __device__ __forceinline__ OscFrame osc_frame_at(const OscArgs &a, int64_t f) {
     const double fr = a.freq ? (double)a.freq[f] : a.p.freq;
@@ -325,14 +342,21 @@ __device__ __forceinline__ OscFrame osc_frame_at(const OscArgs &a, int64_t f) {
     return osc_frame(fr, du, a.p.sample_rate);
 }
 
-// workspace layout (doubles): [0, nb) sums, [nb, 2 nb) offsets, [2 nb, 2 nb + 4) seeds {phase0, y0}
+// workspace layout (doubles): [0, nb) sums, [nb, 2 nb) offsets, [2 nb, 2 nb + 4) seeds {phase0, y0}; a voice owns two
+// of these (dt scan, dy scan), voice after voice
 struct OscWs {
     double *sum, *off, *seed;
 };
-__device__ __forceinline__ OscWs osc_ws(double *ws, int64_t nb) { return {ws, ws + nb, ws + 2 * nb}; }
+__host__ __device__ __forceinline__ int64_t osc_ws_doubles(int64_t nb) { return 2 * nb + 4; }
+__device__ __forceinline__ OscWs osc_ws(double *ws, int64_t nb, int v) {
+    ws += (int64_t)v * (2 * osc_ws_doubles(nb));
+    return {ws, ws + nb, ws + 2 * nb};
+}
 
 // pure rectangle: phase = mod(idx * dt[0], 1) (:185-187)
-__global__ void __launch_bounds__(kOscBlock) k_osc_pure_rect(float *out, OscArgs a) {
+__global__ void __launch_bounds__(kOscBlock) k_osc_pure_rect(float *out, OscArgs bank) {
+    const OscArgs a = osc_voice(bank, blockIdx.y);
+    out += (int64_t)blockIdx.y * a.out_stride;
     const OscFrame fr = osc_frame(a.p.freq, a.p.duty, a.p.sample_rate);
     for (int64_t f = (int64_t)blockIdx.x * kOscBlock + threadIdx.x; f < a.n; f += (int64_t)gridDim.x * kOscBlock) {
         const double phase = pgx::pgx_mod1((double)(a.start + f) * fr.dt);
@@ -345,11 +369,13 @@ __global__ void __launch_bounds__(kOscBlock) k_osc_pure_rect(float *out, OscArgs
 // kPass 1: phases known (pure, or stateful after the dt scan): rectangle -> emit; sawtooth -> sum dy per workgroup.
 // kPass 2: sawtooth: y0 + exclusive prefix of dy -> emit.
 template <bool kPure, int kPass>
-__global__ void __launch_bounds__(kOscBlock) k_osc_pass(float *out, OscArgs a, double *ws_raw, double *ws2_raw,
+__global__ void __launch_bounds__(kOscBlock) k_osc_pass(float *out, OscArgs bank, double *ws_raw, double *ws2_raw,
                                                         int64_t nb) {
     __shared__ double lds[kOscWaves];
-    const OscWs ws = osc_ws(ws_raw, nb);       // dt scan (stateful) / dy scan (pure)
-    const OscWs wy = osc_ws(ws2_raw, nb);      // dy scan (stateful)
+    const OscArgs a = osc_voice(bank, blockIdx.y);
+    out += (int64_t)blockIdx.y * a.out_stride;
+    const OscWs ws = osc_ws(ws_raw, nb, blockIdx.y);       // dt scan (stateful) / dy scan (pure)
+    const OscWs wy = osc_ws(ws2_raw, nb, blockIdx.y);      // dy scan (stateful)
     const int64_t f0 = (int64_t)blockIdx.x * kOscTile + (int64_t)threadIdx.x * kOscT;
     OscFrame fr[kOscT];
     double phase[kOscT];
@@ -407,12 +433,13 @@ __global__ void __launch_bounds__(kOscBlock) k_osc_pass(float *out, OscArgs a, d
 // One workgroup: exclusive scan of the nb workgroup sums.  kWhat 0: the dt scan of the stateful form (seeds the phase
 // from the carried state, or 0 on a restart; carries mod(phase0 + sum dt, 1)).  kWhat 1: the dy scan of the stateful
 // sawtooth (seeds y0 from the carried saw value, or -1 on a restart; carries y0 + sum dy).  kWhat 2: the dy scan of the
-// pure sawtooth (y0 from phase[0], :253-256).
+// pure sawtooth (y0 from phase[0], :253-256).  A workgroup per voice, on the voice's workspace and state.
 template <int kWhat>
 __global__ void __launch_bounds__(kOscBlock) k_osc_scan(double *ws_raw, int64_t nb, double *state, int restart,
-                                                        OscArgs a) {
+                                                        OscArgs bank) {
     __shared__ double lds[kOscWaves];
-    const OscWs ws = osc_ws(ws_raw, nb);
+    const OscWs ws = osc_ws(ws_raw, nb, blockIdx.x);
+    if (kWhat != 2) state += 2 * (int64_t)blockIdx.x;
     double carry = 0.0;
     for (int64_t b0 = 0; b0 < nb; b0 += kOscTile) {
         const int64_t i0 = b0 + (int64_t)threadIdx.x * kOscT;
@@ -440,6 +467,7 @@ __global__ void __launch_bounds__(kOscBlock) k_osc_scan(double *ws_raw, int64_t 
             ws.seed[1] = y0;
             state[1] = y0 + carry;
         } else {
+            const OscArgs a = osc_voice(bank, blockIdx.x);
             const OscFrame fr = osc_frame(a.p.freq, a.p.duty, a.p.sample_rate);
             const double ph0 = pgx::pgx_mod1((double)a.start * fr.dt);
             ws.seed[1] = osc_piecewise(ph0, 1.0 - fr.duty);
@@ -500,27 +528,41 @@ int pgx_karplus_score(float *out, int channels, const pgx_ks_note *notes, int co
 size_t pgx_analog_osc_workspace_bytes(int64_t n) {
     if (n <= 0) return 0;
     const int64_t nb = pgx::ceil_div(n, kOscTile);
-    return (size_t)(2 * (2 * nb + 4)) * sizeof(double);
+    return (size_t)(2 * osc_ws_doubles(nb)) * sizeof(double);
 }
 
-static int osc_launch(float *out, const OscArgs &a, void *workspace, double *state, int restart, bool pure) {
+size_t pgx_analog_osc_bank_workspace_bytes(int64_t n, int batch) {
+    if (n <= 0 || batch <= 0) return 0;
+    return (size_t)batch * pgx_analog_osc_workspace_bytes(n);
+}
+
+// `batch` voices (the single PE: 1, a.params NULL): the voice is the grid's y of a pass and the x of a scan.
+static int osc_launch(float *out, const OscArgs &a, int batch, void *workspace, double *state, int restart,
+                      bool pure) {
     const int64_t nb = pgx::ceil_div(a.n, kOscTile);
     PGX_CHECK_ARG(nb < (int64_t)1 << 31, "pgx_analog_osc: too many frames");
+    PGX_CHECK_ARG(batch <= 65535, "pgx_analog_osc: too many voices");
     double *ws = static_cast<double *>(workspace);
-    double *ws2 = ws + (2 * nb + 4);
-    const dim3 g((unsigned)nb), b(kOscBlock), one(1);
+    double *ws2 = ws + osc_ws_doubles(nb);
+    const dim3 b(kOscBlock), voices((unsigned)batch);
     hipStream_t s = pgx::stream();
+    if (a.p.waveform == 0 && pure) {
+        hipLaunchKernelGGL(k_osc_pure_rect, dim3(pgx::grid_for(a.n, kOscBlock), (unsigned)batch), b, 0, s, out, a);
+        PGX_LAUNCH_CHECK("k_osc_pure_rect");
+        return PGX_OK;
+    }
+    const dim3 g((unsigned)nb, (unsigned)batch);
     const bool saw = a.p.waveform != 0;
     if (pure) {
         hipLaunchKernelGGL((k_osc_pass<true, 1>), g, b, 0, s, out, a, ws, ws2, nb);
-        hipLaunchKernelGGL((k_osc_scan<2>), one, b, 0, s, ws, nb, state, restart, a);
+        hipLaunchKernelGGL((k_osc_scan<2>), voices, b, 0, s, ws, nb, state, restart, a);
         hipLaunchKernelGGL((k_osc_pass<true, 2>), g, b, 0, s, out, a, ws, ws2, nb);
     } else {
         hipLaunchKernelGGL((k_osc_pass<false, 0>), g, b, 0, s, out, a, ws, ws2, nb);
-        hipLaunchKernelGGL((k_osc_scan<0>), one, b, 0, s, ws, nb, state, restart, a);
+        hipLaunchKernelGGL((k_osc_scan<0>), voices, b, 0, s, ws, nb, state, restart, a);
         hipLaunchKernelGGL((k_osc_pass<false, 1>), g, b, 0, s, out, a, ws, ws2, nb);
         if (saw) {
-            hipLaunchKernelGGL((k_osc_scan<1>), one, b, 0, s, ws2, nb, state, restart, a);
+            hipLaunchKernelGGL((k_osc_scan<1>), voices, b, 0, s, ws2, nb, state, restart, a);
             hipLaunchKernelGGL((k_osc_pass<false, 2>), g, b, 0, s, out, a, ws, ws2, nb);
         }
     }
@@ -534,15 +576,9 @@ int pgx_analog_osc_pure(float *out, int64_t start, int64_t n, int channels, doub
     if (n <= 0) return PGX_OK;
     PGX_CHECK_ARG(out && channels >= 1 && sample_rate > 0 && (waveform == 0 || waveform == 1),
                   "pgx_analog_osc_pure: bad argument");
-    OscArgs a{{freq, duty, sample_rate, waveform}, start, n, channels, nullptr, nullptr};
-    if (waveform == 0) {
-        hipLaunchKernelGGL(k_osc_pure_rect, dim3(pgx::grid_for(n, kOscBlock)), dim3(kOscBlock), 0, pgx::stream(), out,
-                           a);
-        PGX_LAUNCH_CHECK("k_osc_pure_rect");
-        return PGX_OK;
-    }
-    PGX_CHECK_ARG(workspace, "pgx_analog_osc_pure: the sawtooth needs a workspace");
-    return osc_launch(out, a, workspace, nullptr, 0, true);
+    PGX_CHECK_ARG(waveform == 0 || workspace, "pgx_analog_osc_pure: the sawtooth needs a workspace");
+    OscArgs a{{freq, duty, sample_rate, waveform}, start, n, channels, nullptr, nullptr, nullptr, 0, 0, 0};
+    return osc_launch(out, a, 1, workspace, nullptr, 0, true);
 }
 
 int pgx_analog_osc_stateful(float *out, int64_t n, int channels, double sample_rate, int waveform, double freq,
@@ -552,8 +588,30 @@ int pgx_analog_osc_stateful(float *out, int64_t n, int channels, double sample_r
     if (n <= 0) return PGX_OK;
     PGX_CHECK_ARG(out && state && workspace && channels >= 1 && sample_rate > 0 && (waveform == 0 || waveform == 1),
                   "pgx_analog_osc_stateful: bad argument");
-    OscArgs a{{freq, duty, sample_rate, waveform}, 0, n, channels, freq_stream, duty_stream};
-    return osc_launch(out, a, workspace, state, restart, false);
+    OscArgs a{{freq, duty, sample_rate, waveform}, 0, n, channels, freq_stream, duty_stream, nullptr, 0, 0, 0};
+    return osc_launch(out, a, 1, workspace, state, restart, false);
+}
+
+int pgx_analog_osc_bank(float *out, int64_t out_stride, int batch, int64_t start, int64_t n, int channels,
+                        double sample_rate, int waveform, const pgx_osc_params *params, const float *freq_streams,
+                        int64_t freq_stride, const float *duty_streams, int64_t duty_stride, int stateful, int restart,
+                        double *state, void *workspace) {
+    PGX_REQUIRE_INIT();
+    PGX_CHECK_ARG(batch >= 0, "pgx_analog_osc_bank: bad argument");
+    if (n <= 0 || batch <= 0) return PGX_OK;
+    PGX_CHECK_ARG(out && params && channels >= 1 && sample_rate > 0 && (waveform == 0 || waveform == 1) &&
+                      out_stride >= n * channels && (!freq_streams || freq_stride >= n) &&
+                      (!duty_streams || duty_stride >= n),
+                  "pgx_analog_osc_bank: bad argument");
+    if (stateful) {
+        PGX_CHECK_ARG(state && workspace, "pgx_analog_osc_bank: the stateful form needs state and workspace");
+    } else {
+        PGX_CHECK_ARG(!freq_streams && !duty_streams, "pgx_analog_osc_bank: the pure form takes no streams");
+        PGX_CHECK_ARG(waveform == 0 || workspace, "pgx_analog_osc_bank: the sawtooth needs a workspace");
+    }
+    OscArgs a{{0.0, 0.0, sample_rate, waveform}, stateful ? 0 : start, n, channels, freq_streams, duty_streams, params,
+              out_stride, freq_stride, duty_stride};
+    return osc_launch(out, a, batch, workspace, stateful ? state : nullptr, stateful ? restart : 0, !stateful);
 }
 
 }  // extern "C"

@@ -109,6 +109,32 @@ k_tuning(float *out, const float *in, int64_t n_elems, const pgx_tuning_op *ops,
     }
 }
 
+// A bank of TransformPEs whose chains hold the same steps with per-voice parameters (voice_bank.py): voice blockIdx.y
+// runs its own nops ops over its own per_voice elements -- k_transform's arithmetic, element for element.
+__global__ void __launch_bounds__(kBlock)
+k_transform_bank(float *out, const float *in, int64_t per_voice, const pgx_transform_op *ops, int nops) {
+    const int64_t stride = (int64_t)gridDim.x * kBlock;
+    const int64_t base = (int64_t)blockIdx.y * per_voice;
+    ops += (int64_t)blockIdx.y * nops;
+    for (int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x; e < per_voice; e += stride) {
+        double v = (double)in[base + e];
+        for (int k = 0; k < nops; ++k) {
+            const pgx_transform_op op = ops[k];
+            switch (op.code) {
+            case 0: v = op.p1 + op.p0 * v; break;
+            case 1: v = v < op.p0 ? op.p0 : (v > op.p1 ? op.p1 : v); break;
+            case 2: v = sqrt(v); break;
+            case 3: v = v * v; break;
+            case 4: v = fabs(v); break;
+            case 5: v = tanh(v); break;
+            case 6: v = 1.0 - v; break;
+            default: break;
+            }
+        }
+        out[base + e] = (float)v;
+    }
+}
+
 __global__ void __launch_bounds__(kBlock)
 k_selftest_tuning(double *out, const double *in, int64_t n, int code, const pgx_tuning_record *tunings,
                   const double *tables) {
@@ -130,6 +156,18 @@ int pgx_tuning(float *out, const float *in, int64_t n_elems, const pgx_tuning_op
     hipLaunchKernelGGL(k_tuning, dim3(pgx::grid_for(n_elems, kBlock)), dim3(kBlock), 0, pgx::stream(), out, in,
                        n_elems, ops, nops, tunings, tables);
     PGX_LAUNCH_CHECK("k_tuning");
+    return PGX_OK;
+}
+
+int pgx_transform_bank(float *out, const float *in, int64_t per_voice, int batch, const pgx_transform_op *ops,
+                       int nops) {
+    PGX_REQUIRE_INIT();
+    PGX_CHECK_ARG(batch >= 0 && batch <= 65535, "pgx_transform_bank: bad argument");
+    if (per_voice <= 0 || batch <= 0) return PGX_OK;
+    PGX_CHECK_ARG(out && in && (ops || nops == 0) && nops >= 0, "pgx_transform_bank: bad argument");
+    hipLaunchKernelGGL(k_transform_bank, dim3(pgx::grid_for(per_voice, kBlock), (unsigned)batch), dim3(kBlock), 0,
+                       pgx::stream(), out, in, per_voice, ops, nops);
+    PGX_LAUNCH_CHECK("k_transform_bank");
     return PGX_OK;
 }
 

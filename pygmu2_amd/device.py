@@ -128,6 +128,7 @@ _SIGNATURES = [
     ("pgx_envelope_scratch_bytes", _Z, [_L, _I]),
     ("pgx_envelope", _I, [_P, _P, _L, _I, _D, _D, _I, _I, _L, _P, _P]),
     ("pgx_transform", _I, [_P, _P, _L, _P, _I]),
+    ("pgx_transform_bank", _I, [_P, _P, _L, _I, _P, _I]),
     ("pgx_tuning", _I, [_P, _P, _L, _P, _I, _P, _P]),
     ("pgx_selftest_tuning", _I, [_P, _P, _L, _I, _P, _P]),
     ("pgx_blitsaw", _I, [_P, _L, _I, _L, _I, _D, _P, _P, _L, _P, _L, _P, _L, _P, _P, _P]),
@@ -182,6 +183,8 @@ _SIGNATURES = [
     ("pgx_analog_osc_workspace_bytes", _Z, [_L]),
     ("pgx_analog_osc_pure", _I, [_P, _L, _L, _I, _D, _I, _D, _D, _P]),
     ("pgx_analog_osc_stateful", _I, [_P, _L, _I, _D, _I, _D, _D, _P, _P, _I, _P, _P]),
+    ("pgx_analog_osc_bank_workspace_bytes", _Z, [_L, _I]),
+    ("pgx_analog_osc_bank", _I, [_P, _L, _I, _L, _L, _I, _D, _I, _P, _P, _L, _P, _L, _I, _I, _P, _P]),
     ("pgx_noise_skip_table", _I, [_P]),
     ("pgx_noise_white", _I, [_P, _L, _I, _L, _U, _P]),
     ("pgx_noise_pink", _I, [_P, _L, _I, _L, _U, _P, _P]),
@@ -221,6 +224,7 @@ TUNING_OP = np.dtype([("code", "<i4"), ("tuning", "<i4"), ("p0", "<f8"), ("p1", 
 TUNING_RECORD = np.dtype([("reference_pitch", "<f8"), ("reference_freq", "<f8"), ("divisions", "<f8"),
                           ("table_offset", "<i8"), ("num_notes", "<i4"), ("pad", "<i4")])
 GATE_PARAMS = np.dtype([("dt", "<f8"), ("phase", "<f8"), ("duty", "<f8")])
+OSC_PARAMS = np.dtype([("freq", "<f8"), ("duty", "<f8")])
 KS_PARAMS = np.dtype([("line_offset", "<i8"), ("n", "<i4"), ("two_phase", "<i4"), ("switch_at", "<i8"),
                       ("rho", "<f4"), ("rho_damping", "<f4"), ("c", "<f4"), ("pad", "<f4")])
 KS_STATE = np.dtype([("r", "<i4"), ("ap_in", "<f4"), ("ap_out", "<f4"), ("pad", "<i4")])

@@ -11,10 +11,19 @@ K voices in input order in float32 -- the same additions, in the same order, as 
 The batched kernels are the very same kernels the single PEs use (batch = 1 there), so a
 bank produces the same samples as rendering the voices one by one.
 
-Supported nodes: SinePE (scalar), BlitSawPE (scalar), SuperSawPE (scalar), BiquadPE
-(constant coefficients), LadderPE (scalar controls), CombPE (scalar controls), GainPE (constant or PE gain),
-AdsrGatedPE, PeriodicGate.  Anything else -> `try_build_bank` returns None and MixPE
-falls back to per-input rendering.
+Supported nodes: SinePE (scalar), BlitSawPE (scalar), SuperSawPE (scalar), AnalogOscPE (scalar parameters, or
+single-channel PEs of batchable classes), BiquadPE (constant coefficients), LadderPE (scalar controls), CombPE (scalar
+controls), GainPE (constant or PE gain), TransformPE (a chain lowered to pgx_transform), AdsrGatedPE, PeriodicGate.
+Anything else -> `try_build_bank` returns None and MixPE falls back to per-input rendering.
+
+AnalogOscPE voices (pgx_analog_osc_bank): the voice is a grid dimension of the PE's own scan kernels, so a bank of K
+takes the launches of one PE -- 1 (pure rectangle), 3 (pure sawtooth, stateful rectangle), 5 (stateful sawtooth) -- and
+gives each voice the PE's samples bit for bit.  Frequency and duty may be PEs (the reference's PWM voice: duty =
+TransformPE(SinePE, Affine)): they are batched levels of their own, rendered first; phase and saw value are carried
+per voice in a [K][2] state blob under the PE's restart rule.  The pure sawtooth restarts its integration at every
+request (analog_osc_pe.py), so a bank that holds one renders exactly the requests it is given: no windows
+(_Node._REQUEST_DEPENDENT).  A voice tree that holds an AnalogOscPE is banked from ANALOG_OSC_MIN_VOICES voices on: below,
+over a long stream, the per-voice path's look-ahead windows are faster than a bank rendered block by block (measured).
 """
 
 from __future__ import annotations
@@ -27,7 +36,9 @@ import numpy as np
 
 from . import device as _dev
 from ._kernels import DeviceBuffer, blitsaw_workspace, check, lib, ptr
+from . import transforms as _tf
 from .adsr_pe import AdsrGatedPE
+from .analog_osc_pe import AnalogOscPE
 from .biquad_pe import BiquadPE, rbj_coefficients, settle_frames, settle_frames_fine
 from .blit_saw_pe import BlitSawPE, wide_oscillators_ok
 from .comb_pe import CombPE
@@ -39,8 +50,15 @@ from .processing_element import ProcessingElement
 from .sine_pe import SinePE
 from .snippet import Snippet
 from .super_saw_pe import SuperSawPE
+from .transform_pe import TransformPE
 
 MIN_VOICES = 4
+ANALOG_OSC_MIN_VOICES = 64    # ... and for voices that hold an AnalogOscPE.  The per-voice path streams through look-ahead's
+                              # windows of up to 256 blocks, a bank block by block: tools/analog_bank_probe.py, PWM voice under
+                              # an envelope, us per block bank / per voice over a long stream -- 4 096-frame blocks: 4 voices
+                              # 55 / 8, 8: 48 / 14, 64: 50 / 120, 512: 94 / 1 728; 48 000-frame blocks: 52 / 46, 43 / 85, 80 / 767,
+                              # 377 / 11 733 (streams of 8 blocks: the bank from 4 voices on, 62 / 96 ... 451 / 49 040).  The
+                              # smallest K measured from which the bank wins every row, and every row of a larger K
 BANK_WINDOWS = True           # a small bank streamed in equal blocks: 2, 4, 8 blocks per render, handed out as rows (VoiceBank)
 BANK_WINDOWS_ANY_ROOT = os.environ.get("PGX_BANK_WINDOWS_ANY_ROOT", "0") == "1"     # experiments (C5: measured slower)
 BANK_WINDOW_FIRST = 2
@@ -240,6 +258,7 @@ class _Node:
 
     # ---- what VoiceBank's windows need of a node: its carried state by name, and a way to come to rest
     _STATE = ()                  # attributes (DeviceBuffers, numbers, None) that make up the carried state
+    _REQUEST_DEPENDENT = False   # the samples depend on how the stream is cut into requests: VoiceBank opens no window
 
     def quiesce(self, keep=None) -> None:
         """Anything rendered ahead of the stream is dropped: the states are where the last block handed out left them."""
@@ -503,6 +522,85 @@ class _SuperSawNode(_SawNode):
             self.last_end = start + n
             return out
         return self.sum_voices(self.take_voices(start, n), n)
+
+
+class _AnalogOscNode(_Node):
+    """Bank of AnalogOscPEs of one waveform: pgx_analog_osc_bank, the PE's kernels with the voice in the grid.  Scalar
+    parameters only: the pure form, a function of the frame index (and, for the sawtooth, of where the request begins).
+    A PE-valued frequency or duty cycle: the stateful form -- the children's [K][n][1] streams first, then the bank,
+    phase and saw value carried per voice in `state`."""
+
+    _STATE = ("state", "last_end")
+
+    def __init__(self, pes, children):
+        super().__init__(pes, children)
+        rec = np.zeros(self.k, dtype=_dev.OSC_PARAMS)
+        for i, pe in enumerate(pes):          # (the scalar of a PE-valued parameter is never read: 0.0 as in the PE's render)
+            rec[i] = (0.0 if _is_pe(pe._frequency) else float(pe._frequency),
+                      0.0 if _is_pe(pe._duty_cycle) else float(pe._duty_cycle))
+        self.params = _dev.upload_structs(rec)
+        self.wave = 0 if pes[0]._waveform == AnalogOscPE.WAVE_RECTANGLE else 1
+        self.ch = pes[0]._channels
+        self.stateful = bool(children)
+        self.state = DeviceBuffer((self.k, 2), np.float64, zero=True) if self.stateful else None
+        self.last_end = None
+        self.ws = None
+        self._REQUEST_DEPENDENT = not self.stateful and self.wave == 1
+
+    def reset(self):
+        super().reset()
+        self.last_end = None          # the next render restarts at phase 0 / saw -1 (AnalogOscPE._reset_state)
+
+    def channels(self):
+        return self.ch
+
+    def render(self, start, n):
+        L = lib()
+        freq = self.children["frequency"].render(start, n) if "frequency" in self.children else None
+        duty = self.children["duty"].render(start, n) if "duty" in self.children else None
+        if self.stateful or self.wave:
+            need = L.pgx_analog_osc_bank_workspace_bytes(n, self.k)
+            if self.ws is None or self.ws.nbytes < need:
+                self.ws = DeviceBuffer((need,), np.uint8)
+        out = DeviceBuffer((self.k, n, self.ch), np.float32)
+        # the PE's own rule (AnalogOscPE._render): a render that does not continue the previous one starts over
+        restart = self.stateful and (self.last_end is None or start != self.last_end)
+        check(L.pgx_analog_osc_bank(out.ptr, n * self.ch, self.k, start, n, self.ch, self.sr, self.wave,
+                                    self.params.ptr, ptr(freq), n, ptr(duty), n, int(self.stateful), int(restart),
+                                    ptr(self.state), ptr(self.ws)), "pgx_analog_osc_bank")
+        if self.stateful:
+            self.last_end = start + n
+        return out
+
+
+class _TransformNode(_Node):
+    """Bank of TransformPEs whose chains hold the same steps.  The same parameters in every voice (the PWM voice's
+    Affine(0.4, 0.5)): one pgx_transform over the stacked K * n * channels elements.  Per-voice parameters (a pitch
+    envelope's Affine(300, f_i)): pgx_transform_bank, one launch as well, each voice under its own ops."""
+
+    def __init__(self, pes, children):
+        super().__init__(pes, children)
+        programs = [pe._lowered.ops() for pe in pes]
+        self.nops = len(programs[0])
+        self.uniform = all(program == programs[0] for program in programs)
+        table = np.zeros((1 if self.uniform else self.k, max(self.nops, 1)), dtype=_dev.TRANSFORM_OP)
+        for i, program in enumerate(programs[:table.shape[0]]):
+            for j, (code, p0, p1) in enumerate(program):
+                table[i, j] = (code, 0, p0, p1)
+        self.ops = DeviceBuffer.from_host(table.view(np.uint8))
+
+    def channels(self):
+        return self.children["source"].channels()
+
+    def render(self, start, n):
+        x = self.children["source"].render(start, n)
+        k, _, ch = x.shape
+        out = DeviceBuffer((k, n, ch), np.float32)
+        if self.uniform:
+            check(lib().pgx_transform(out.ptr, x.ptr, k * n * ch, self.ops.ptr, self.nops), "pgx_transform")
+        else:
+            check(lib().pgx_transform_bank(out.ptr, x.ptr, n * ch, k, self.ops.ptr, self.nops), "pgx_transform_bank")
+        return out
 
 
 class _BiquadNode(_Node):
@@ -1068,15 +1166,43 @@ class _Kind(NamedTuple):
     extras: object               # (pe) -> what else goes into the key, or None
     children: tuple              # ((name the node knows the child by, attribute of the PE that holds it, present(pe)), ...)
     node: type                   # node(pes, children); node(pes) for a class without children
+    min_voices: object = None    # () -> voices below which a tree that holds this class is not banked (None: MIN_VOICES)
 
 
 _ALWAYS = lambda pe: True
 _SOURCE = ("source", "_source", _ALWAYS)
+
+
+def _osc_batchable(pe) -> bool:
+    """Parameter PEs as (n, 1) streams only (what the kernel reads; the PE itself takes channel 0 of anything)."""
+    return all(p.channel_count() == 1 for p in pe.inputs())
+
+
+def _transform_codes(pe):
+    """The op codes of a TransformPE's device program -- what two voices must share to be one launch (their
+    parameters may differ: _TransformNode) --, or None: a host callable, a chain that follows temperament.py's
+    globals (resolved when a block is rendered), a tuning step (pgx_tuning's program, not pgx_transform's)."""
+    if pe._lowered is None or pe._follows_globals:
+        return None
+    try:
+        codes = tuple(op[0] for op in pe._lowered.ops())
+    except LookupError:
+        return None
+    return None if any(code in _tf.TUNING_CODES for code in codes) else codes
+
+
 _KINDS = (
     _Kind(SinePE, "sine", lambda pe: not pe._has_pe_inputs(), lambda pe: (pe._channels,), (), _SineNode),
     _Kind(BlitSawPE, "blitsaw", lambda pe: not pe.inputs(), lambda pe: (pe._channels,), (), _BlitSawNode),
     _Kind(SuperSawPE, "supersaw", lambda pe: not pe.inputs(), lambda pe: (pe._channels, len(pe._oscillators)), (),
           _SuperSawNode),
+    # (which parameters are PEs is part of the key: a frequency child and a duty child may have the same key)
+    _Kind(AnalogOscPE, "analog_osc", _osc_batchable,
+          lambda pe: (pe._waveform, pe._channels, _is_pe(pe._frequency), _is_pe(pe._duty_cycle)),
+          (("frequency", "_frequency", lambda pe: _is_pe(pe._frequency)),
+           ("duty", "_duty_cycle", lambda pe: _is_pe(pe._duty_cycle))), _AnalogOscNode, lambda: ANALOG_OSC_MIN_VOICES),
+    _Kind(TransformPE, "transform", lambda pe: _transform_codes(pe) is not None, lambda pe: (_transform_codes(pe),),
+          (_SOURCE,), _TransformNode),
     _Kind(BiquadPE, "biquad", lambda pe: not (pe._freq_is_pe or pe._q_is_pe), None, (_SOURCE,), _BiquadNode),
     _Kind(LadderPE, "ladder", lambda pe: not (pe._freq_is_pe or pe._res_is_pe or pe._drive_is_pe), None, (_SOURCE,),
           _LadderNode),
@@ -1112,6 +1238,16 @@ def _signature(pe):
     return key
 
 
+def _min_voices(pe) -> int:
+    """Voices from which trees like `pe` (batchable: _signature) are banked: the largest minimum of a class in the tree."""
+    kind = _kind(pe)
+    need = kind.min_voices() if kind.min_voices is not None else MIN_VOICES
+    for _, attribute, present in kind.children:
+        if present(pe):
+            need = max(need, _min_voices(getattr(pe, attribute)))
+    return need
+
+
 def _collect_ids(pe, seen):
     if id(pe) in seen:
         return False
@@ -1136,6 +1272,7 @@ class VoiceBank(_Windowed):
         if isinstance(self.root, _LadderNode):
             self.root.is_root = True
         self.mix_windows = False     # windows at the level of the mix whatever the root (set_mix_windows)
+        self.request_dependent = any(node._REQUEST_DEPENDENT for node in self._nodes())     # (a pure sawtooth: no windows)
         self._reset_windows(BANK_WINDOW_FIRST)       # win.buf: the mixed window (Snippet), win.undo: [(node, snapshot)]
         self.streaming = False       # the block being rendered continues the one before it, same length
 
@@ -1192,7 +1329,8 @@ class VoiceBank(_Windowed):
         # when the stream ends: 97 -> 155 us; not the C5 graph -- its envelope walk and mixes do not shrink with the
         # block, 56 -> 93 us for 64 voices.  A ladder root has windows of its own.)
         on_chip = VOICE_TILE_WINDOWS and self._mixes_on_chip(duration)
-        if (BANK_WINDOWS and streaming and (self.k <= BANK_WINDOW_MAX_VOICES or on_chip) and duration >= 4096
+        if (BANK_WINDOWS and streaming and not self.request_dependent
+                and (self.k <= BANK_WINDOW_MAX_VOICES or on_chip) and duration >= 4096
                 and (isinstance(self.root, _SuperSawNode) and not self.root.fused() or BANK_WINDOWS_ANY_ROOT
                      or self.mix_windows or on_chip)
                 and not lib().pgx_stream_is_forked()):
@@ -1346,11 +1484,12 @@ class VoiceBank(_Windowed):
 
 
 def try_build_bank(inputs):
-    """VoiceBank for `inputs` if they are >= MIN_VOICES identical, private, batchable trees."""
+    """VoiceBank for `inputs` if they are >= MIN_VOICES (_min_voices: some classes ask for more) identical, private,
+    batchable trees."""
     if len(inputs) < MIN_VOICES:
         return None
     sig0 = _signature(inputs[0])
-    if sig0 is None:
+    if sig0 is None or len(inputs) < _min_voices(inputs[0]):
         return None
     seen = set()
     for pe in inputs:
