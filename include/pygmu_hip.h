@@ -924,7 +924,12 @@ int pgx_noise_brown(float *out, int64_t out_stride, int batch, int64_t n, uint64
  * Bluestein's chirp-z over M = 2^ceil(log2(2n - 1)) points with the chirp phase k^2 mod 2n reduced in 64-bit
  * integers.  Every twiddle is evaluated in float64 from an exactly reduced index, never recurred.
  *   pgx_dft_plan_bytes / pgx_dft_plan   what depends on n alone (the chirp and its spectrum; for a power of two the
- *                                       plan is empty but must still be a valid 16-byte block), made once per length
+ *                                       plan is empty but must still be a valid 16-byte block), made once per length.
+ *                                       Layout, in {double re, im} points, M as above:
+ *                                         chirp[n]     b_k = exp(i*pi*k^2/n), k < n
+ *                                         spectrum[M]  the forward DFT of b wrapped to M points: b_j for j < n,
+ *                                                      b_(M-j) for j > M - n, 0 between
+ *                                         scratch[M]   only when M > 2048: the column pass of that DFT; not read again
  *   pgx_dft_workspace_bytes             scratch of one call; 0 for an unsupported n or batch
  *   pgx_dft_c2c                         out == in is allowed; out, in, plan and workspace are device memory
  * The three *_bytes helpers and pgx_dft_max_length are pure planning helpers: they need no device.  A longer n is
