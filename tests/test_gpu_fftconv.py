@@ -1,8 +1,10 @@
 """
 GPU: the FFT overlap-save path of ConvolvePE (pgx_convolve_fft) against numpy's float64
-convolution and against the direct MFMA path, over geometries that exercise every branch:
+convolution, over geometries that exercise every branch:
 square and non-square N1 x N2, odd and even numbers of overlap-save blocks (packed pairs),
 blocks shorter than the filter, carried history, every channel rule.
+The comparison against the direct MFMA path (pgx_convolve) on the same inputs is
+test_direct_and_fft_paths_agree in tests/test_gpu_convolve_direct.py.
 """
 
 import numpy as np
