@@ -250,6 +250,22 @@ int pgx_biquad_varying(float *out, const float *in, int64_t n, int channels, dou
                        const pgx_biquad_var_params *params, const float *freq, const float *q,
                        double gain_a, double gain_sqrt_a, double *state /* [channels][4] */,
                        void *workspace);
+/* Bank of BiquadPEs with PE-driven frequency and / or Q (voice_bank.py): pgx_biquad_varying with the voice in the grid.
+ * in / out: `batch` rows of n * channels float32, in_stride / out_stride elements apart (each >= n * channels);
+ * freq / q: NULL (voice v takes params[v].freq / params[v].q) or `batch` rows of n float32, freq_stride / q_stride apart (>= n);
+ * params: device [batch] (mode and the scalars are per voice);  gains: device [batch][2] = {A, sqrt(A)}, the two numbers the
+ *         host passes pgx_biquad_varying by value, per voice;  state: [batch][channels][4];
+ * workspace: batch * pgx_scan2_workspace_bytes(n, channels) bytes (voice v's slice starts at v times that), or NULL.
+ * With a workspace every voice is rendered by pgx_biquad_varying's own plan (scan2_plan(n): the reduce and the apply launch,
+ * grid (segments, channels, batch)); without one, or for blocks of one or two tiles, one workgroup per (voice, channel) walks
+ * the block in ONE launch.  Either way row v holds the float32 samples and the final state that
+ * pgx_biquad_varying(row v, ..., the same choice of workspace) gives, bit for bit.
+ * n <= 0 or batch <= 0: PGX_OK, nothing launched.  batch > 65535, a stride below its row, a null out / in / params / gains /
+ * state: PGX_ERR_INVALID, nothing launched. */
+int pgx_biquad_varying_bank(float *out, int64_t out_stride, const float *in, int64_t in_stride, int batch, int64_t n,
+                            int channels, double sample_rate, const pgx_biquad_var_params *params, const double *gains,
+                            const float *freq, int64_t freq_stride, const float *q, int64_t q_stride,
+                            double *state, void *workspace);
 
 /* ------------------------------------------------------------------ SVFilterPE / EnvelopePE / TransformPE
  * (the PEs of benchmarks/profile_biquad_vs_svfilter.py)

@@ -3463,6 +3463,134 @@ k_biquad_varying(float *out, const float *in, int64_t n, int channels, double sr
     }
 }
 
+// Bank of time-varying biquads (pgx_biquad_varying_bank, voice_bank.py): k_biquad_varying with the voice in blockIdx.z.
+// What differs is where a workgroup's data lies -- row v of in / out / freq / qs, params[v], gains[2v .. 2v + 1],
+// state[v][channel], voice v's slice of the workspace (ws_doubles doubles each: snapshot[channel], agg[channel][seg]);
+// from `p` on the body is k_biquad_varying's, operation for operation, so a (voice, channel, segment) workgroup writes
+// the bits the single kernel writes for that voice.  p.mode, A and sqrtA are uniform over the workgroup, as there.
+template <int MODE>
+__global__ void __launch_bounds__(kBlock)
+k_biquad_varying_bank(float *out, int64_t out_stride, const float *in, int64_t in_stride, int64_t n, int channels,
+                      double sr, const pgx_biquad_var_params *params, const double *gains, const float *freq,
+                      int64_t freq_stride, const float *qs, int64_t q_stride, double *state, double *workspace,
+                      int64_t ws_doubles, int seg_tiles, int nseg) {
+    __shared__ BvShared sh;
+    const int tid = threadIdx.x;
+    const int seg = blockIdx.x, ch = blockIdx.y;
+    const int64_t v = blockIdx.z;
+    out += v * out_stride;
+    in += v * in_stride;
+    if (freq) freq += v * freq_stride;
+    if (qs) qs += v * q_stride;
+    const pgx_biquad_var_params p = params[v];
+    const double A = gains[2 * v], sqrtA = gains[2 * v + 1];
+    double *snapshot = workspace ? workspace + v * ws_doubles : nullptr;
+    double *agg = snapshot ? snapshot + (int64_t)channels * 4 : nullptr;
+    double *st = state + (v * channels + ch) * 4;   // x1,x2,y1,y2
+    const double *init = (MODE == 1) ? snapshot + ch * 4 : st;
+    const double sx1 = init[0], sx2 = init[1];
+    double *ag = agg + ((int64_t)ch * nseg) * 6;
+    V2 carry{init[2], init[3]};                     // (y1, y2)
+    if (MODE == 1) carry = scan2_fold(ag, seg, carry);
+    if (MODE == 0 && seg == 0 && tid < 4) snapshot[ch * 4 + tid] = st[tid];
+    M2 acc_m = m_identity();
+    V2 acc_v{0.0, 0.0};
+    V2 final_y{0.0, 0.0};
+    bool have_final = false;
+
+    const int64_t tile0 = (int64_t)seg * seg_tiles;
+    for (int t = 0; t < seg_tiles; ++t) {
+        const int64_t base = (tile0 + t) * kBvTile;
+        if (base >= n) break;
+        const int64_t f0 = base + (int64_t)tid * kBvT;
+        double ff[kBvT], ca1[kBvT], ca2[kBvT];
+        double xm1, xm2;
+        {
+            int64_t i1 = f0 - 1, i2 = f0 - 2;
+            xm1 = (i1 >= 0) ? ((i1 < n) ? (double)in[i1 * channels + ch] : 0.0) : (i1 == -1 ? sx1 : sx2);
+            xm2 = (i2 >= 0) ? ((i2 < n) ? (double)in[i2 * channels + ch] : 0.0) : (i2 == -1 ? sx1 : sx2);
+        }
+        M2 cm = m_identity();
+        V2 cv{0.0, 0.0};
+        // loads first, unconditionally, at a clamped index (see k_biquad_varying): never past the row's n frames
+        float x_in[kBvT], f_in[kBvT], q_in[kBvT];
+#pragma unroll
+        for (int j = 0; j < kBvT; ++j) {
+            const int64_t at = (f0 + j < n) ? f0 + j : n - 1;
+            x_in[j] = in[at * channels + ch];
+        }
+        if (freq) {
+#pragma unroll
+            for (int j = 0; j < kBvT; ++j) f_in[j] = freq[(f0 + j < n) ? f0 + j : n - 1];
+        }
+        if (qs) {
+#pragma unroll
+            for (int j = 0; j < kBvT; ++j) q_in[j] = qs[(f0 + j < n) ? f0 + j : n - 1];
+        }
+#pragma unroll
+        for (int j = 0; j < kBvT; ++j) {
+            const bool live = (f0 + j < n);
+            double x = live ? (double)x_in[j] : 0.0;
+            double f = p.freq, q = p.q;
+            if (freq) f = live ? (double)f_in[j] : 1000.0;
+            if (qs) q = live ? (double)q_in[j] : 1.0;
+            double b0, b1, b2, a1, a2;
+            rbj(p.mode, f, q, A, sqrtA, sr, b0, b1, b2, a1, a2);
+            ff[j] = (b0 * x + b1 * xm1) + b2 * xm2;
+            ca1[j] = a1;
+            ca2[j] = a2;
+            xm2 = xm1;
+            xm1 = x;
+            if (live) {
+                M2 nm;
+                nm.a = -a1 * cm.a - a2 * cm.c;
+                nm.b = -a1 * cm.b - a2 * cm.d;
+                nm.c = cm.a;
+                nm.d = cm.b;
+                V2 nv;
+                nv.x = (ff[j] - a1 * cv.x) - a2 * cv.y;
+                nv.y = cv.x;
+                cm = nm;
+                cv = nv;
+            }
+        }
+        V2 s = scan2_tile<MODE>(sh, cm, cv, carry, acc_m, acc_v);
+        if (MODE == 0) continue;
+
+        float yf[kBvT];
+#pragma unroll
+        for (int j = 0; j < kBvT; ++j) {
+            double y0 = (ff[j] - ca1[j] * s.x) - ca2[j] * s.y;
+            yf[j] = (float)y0;
+            if (f0 + j < n) {
+                s.y = s.x;
+                s.x = y0;
+            }
+            if (f0 + j == n - 1) {
+                final_y = s;
+                have_final = true;
+            }
+        }
+        store_frames<kBvT>(out, f0, n, channels, ch, yf);
+    }
+    if (MODE == 0) {
+        if (tid == 0) {
+            double *a = ag + (int64_t)seg * 6;
+            a[0] = acc_m.a; a[1] = acc_m.b; a[2] = acc_m.c; a[3] = acc_m.d; a[4] = acc_v.x; a[5] = acc_v.y;
+        }
+        return;
+    }
+    if (have_final) {
+        // the state rule of k_biquad_varying: x2 is the previous x1 when n == 1
+        double nx1 = (double)in[(n - 1) * channels + ch];
+        double nx2 = (n >= 2) ? (double)in[(n - 2) * channels + ch] : sx1;
+        st[0] = nx1;
+        st[1] = nx2;
+        st[2] = final_y.x;
+        st[3] = final_y.y;
+    }
+}
+
 // ================================================================================================
 // PeriodicGate with PE-driven frequency / duty / phase: FunctionGenPE's stateful rectangle path
 // (function_gen_pe.py:157-193): base = mod(phase0 + [0, cumsum(f/sr)[:-1]], 1); gate = mod(base + ph, 1) < duty.
@@ -4506,6 +4634,40 @@ int pgx_biquad_varying(float *out, const float *in, int64_t n, int channels, dou
                        channels, sample_rate, params, freq, q, gain_a, gain_sqrt_a, state, snap, agg, p.seg_tiles,
                        p.nseg);
     PGX_LAUNCH_CHECK("k_biquad_varying<apply>");
+    return PGX_OK;
+}
+
+// The same plan per voice, the voice in grid.z (<= 65535); voice v's snapshot and maps lie at v times the single
+// entry's workspace size.
+int pgx_biquad_varying_bank(float *out, int64_t out_stride, const float *in, int64_t in_stride, int batch, int64_t n,
+                            int channels, double sample_rate, const pgx_biquad_var_params *params, const double *gains,
+                            const float *freq, int64_t freq_stride, const float *q, int64_t q_stride, double *state,
+                            void *workspace) {
+    PGX_REQUIRE_INIT();
+    if (n <= 0 || batch <= 0) return PGX_OK;
+    PGX_CHECK_ARG(out && in && params && gains && state && channels >= 1 && sample_rate > 0 && batch <= 65535,
+                  "pgx_biquad_varying_bank: bad argument");
+    PGX_CHECK_ARG(out_stride >= n * channels && in_stride >= n * channels && (!freq || freq_stride >= n) &&
+                      (!q || q_stride >= n),
+                  "pgx_biquad_varying_bank: a stride below its row");
+    const Scan2Plan p = scan2_plan(n, kBvTile);
+    double *ws = (double *)workspace;
+    const int64_t ws_doubles = (int64_t)channels * (4 + (int64_t)p.nseg * 6);      // pgx_scan2_workspace_bytes / 8
+    if (p.nseg <= 1 || workspace == nullptr) {
+        hipLaunchKernelGGL(k_biquad_varying_bank<2>, dim3(1, channels, batch), dim3(kBlock), 0, pgx::stream(), out,
+                           out_stride, in, in_stride, n, channels, sample_rate, params, gains, freq, freq_stride, q,
+                           q_stride, state, (double *)nullptr, (int64_t)0, (int)pgx::ceil_div(n, kBvTile), 1);
+        PGX_LAUNCH_CHECK("k_biquad_varying_bank");
+        return PGX_OK;
+    }
+    hipLaunchKernelGGL(k_biquad_varying_bank<0>, dim3(p.nseg, channels, batch), dim3(kBlock), 0, pgx::stream(), out,
+                       out_stride, in, in_stride, n, channels, sample_rate, params, gains, freq, freq_stride, q, q_stride,
+                       state, ws, ws_doubles, p.seg_tiles, p.nseg);
+    PGX_LAUNCH_CHECK("k_biquad_varying_bank<reduce>");
+    hipLaunchKernelGGL(k_biquad_varying_bank<1>, dim3(p.nseg, channels, batch), dim3(kBlock), 0, pgx::stream(), out,
+                       out_stride, in, in_stride, n, channels, sample_rate, params, gains, freq, freq_stride, q, q_stride,
+                       state, ws, ws_doubles, p.seg_tiles, p.nseg);
+    PGX_LAUNCH_CHECK("k_biquad_varying_bank<apply>");
     return PGX_OK;
 }
 

@@ -95,6 +95,7 @@ _SIGNATURES = [
     ("pgx_biquad_sine_set_runs", _I, [_I]),
     ("pgx_biquad_sine_runs_plan", _I, [_L, _L, C.POINTER(_I)]),
     ("pgx_biquad_varying", _I, [_P, _P, _L, _I, _D, _P, _P, _P, _D, _D, _P, _P]),
+    ("pgx_biquad_varying_bank", _I, [_P, _L, _P, _L, _I, _L, _I, _D, _P, _P, _P, _L, _P, _L, _P, _P]),
     ("pgx_scan2_workspace_bytes", _Z, [_L, _I]),
     ("pgx_convolve_fft_size", _L, [_L]),
     ("pgx_convolve_fft_spectrum_bytes", _Z, [_L, _I]),

@@ -12,9 +12,18 @@ The batched kernels are the very same kernels the single PEs use (batch = 1 ther
 bank produces the same samples as rendering the voices one by one.
 
 Supported nodes: SinePE (scalar), BlitSawPE (scalar), SuperSawPE (scalar), AnalogOscPE (scalar parameters, or
-single-channel PEs of batchable classes), BiquadPE (constant coefficients), LadderPE (scalar controls), CombPE (scalar
-controls), GainPE (constant or PE gain), TransformPE (a chain lowered to pgx_transform), AdsrGatedPE, PeriodicGate.
+single-channel PEs of batchable classes), BiquadPE (constant coefficients, or cutoff and / or Q driven by single-channel
+PEs of batchable classes), LadderPE (scalar controls), CombPE (scalar controls), GainPE (constant or PE gain), TransformPE
+(a chain lowered to pgx_transform), AdsrGatedPE, PeriodicGate.
 Anything else -> `try_build_bank` returns None and MixPE falls back to per-input rendering.
+
+Swept-filter voices (pgx_biquad_varying_bank, _BiquadVarNode): a BiquadPE whose cutoff or Q is a PE -- an oscillator into a
+low-pass that follows an envelope or an LFO -- is a kind of its own, key ("biquad_var", freq_is_pe, q_is_pe, source, ...);
+mode, gain_db and the scalar of the other parameter are per-voice data.  The modulators are batched levels rendered first,
+then ONE call runs pgx_biquad_varying's plan with the voice in the grid: each voice's samples and {x1, x2, y1, y2} are the
+PE's, bit for bit.  From BIQUAD_VAR_WALK_MIN_ROWS rows (voices x channels) on the node passes no workspace: every row is
+walked by one workgroup in one launch, the same recurrence in another association (within a float32 rounding).  Banked
+from BIQUAD_VAR_MIN_VOICES voices on (both measured: tools/swept_bank_probe.py).
 
 AnalogOscPE voices (pgx_analog_osc_bank): the voice is a grid dimension of the PE's own scan kernels, so a bank of K
 takes the launches of one PE -- 1 (pure rectangle), 3 (pure sawtooth, stateful rectangle), 5 (stateful sawtooth) -- and
@@ -29,6 +38,7 @@ over a long stream, the per-voice path's look-ahead windows are faster than a ba
 from __future__ import annotations
 
 import functools
+import math
 import os
 from typing import NamedTuple
 
@@ -39,7 +49,7 @@ from ._kernels import DeviceBuffer, blitsaw_workspace, check, lib, ptr
 from . import transforms as _tf
 from .adsr_pe import AdsrGatedPE
 from .analog_osc_pe import AnalogOscPE
-from .biquad_pe import BiquadPE, rbj_coefficients, settle_frames, settle_frames_fine
+from .biquad_pe import _MODE_INDEX, BiquadPE, rbj_coefficients, settle_frames, settle_frames_fine
 from .blit_saw_pe import BlitSawPE, wide_oscillators_ok
 from .comb_pe import CombPE
 from .extent import Extent
@@ -59,6 +69,18 @@ ANALOG_OSC_MIN_VOICES = 64    # ... and for voices that hold an AnalogOscPE.  Th
                               # 55 / 8, 8: 48 / 14, 64: 50 / 120, 512: 94 / 1 728; 48 000-frame blocks: 52 / 46, 43 / 85, 80 / 767,
                               # 377 / 11 733 (streams of 8 blocks: the bank from 4 voices on, 62 / 96 ... 451 / 49 040).  The
                               # smallest K measured from which the bank wins every row, and every row of a larger K
+BIQUAD_VAR_MIN_VOICES = 16    # ... and for voices that hold a BiquadPE with a PE-driven cutoff or Q (_BiquadVarNode), for the same
+                              # reason: tools/swept_bank_probe.py, sawtooth -> swept low-pass under an envelope, us per block bank /
+                              # per voice over a stream of 248 blocks -- 4 096-frame blocks: 4 voices 57 / 26, 8: 48 / 46, 16: 49 / 90,
+                              # 64: 66 / 362, 512: 132 / 2 990; 48 000-frame blocks: 63 / 56, 72 / 107, 84 / 219, 166 / 851,
+                              # 727 / 7 231 (streams of 8 blocks: the bank from 4 voices on, 70 / 137 ... 807 / 40 556).  The smallest
+                              # K measured from which the bank wins every row, and every row of a larger K
+BIQUAD_VAR_WALK_MIN_ROWS = 512   # rows (voices x channels) from which _BiquadVarNode passes no workspace: one workgroup per row walks
+                              # the block in one launch instead of the segmented plan's two.  The same probe, us per block walk /
+                              # segmented, streams of 8 and of 248 blocks -- 4 096 frames: 256 rows 102 / 90 and 78 / 88, 512 rows
+                              # 120 / 141 and 112 / 132; 48 000 frames: 16 rows 231 / 91, 64: 271 / 179, 256: 344 / 435 and 308 / 392,
+                              # 512: 521 / 807 and 470 / 727.  The smallest row count measured from which the walk is not slower in
+                              # any row, and in no row of a larger count (256 loses one of its four: short streams of 4 096 frames)
 BANK_WINDOWS = True           # a small bank streamed in equal blocks: 2, 4, 8 blocks per render, handed out as rows (VoiceBank)
 BANK_WINDOWS_ANY_ROOT = os.environ.get("PGX_BANK_WINDOWS_ANY_ROOT", "0") == "1"     # experiments (C5: measured slower)
 BANK_WINDOW_FIRST = 2
@@ -760,6 +782,61 @@ class _BiquadNode(_Node):
         return out
 
 
+class _BiquadVarNode(_Node):
+    """Bank of BiquadPEs whose cutoff and / or Q is a PE (the swept filter of a subtractive voice):
+    pgx_biquad_varying_bank, the PE's kernel with the voice in the grid.  The children's [K][n][ch] and [K][n][1] streams
+    first, then one call; mode, gain_db and the scalar of a parameter that is no PE are per voice (`params`, `gains`),
+    {x1, x2, y1, y2} is carried per voice and channel in `state`.  (No subclass of _BiquadNode: it takes none of the
+    on-chip mixes VoiceBank chooses by that class.)"""
+
+    _STATE = ("state",)
+
+    def __init__(self, pes, children):
+        super().__init__(pes, children)
+        rec = np.zeros(self.k, dtype=_dev.BIQUAD_VAR_PARAMS)
+        gains = np.zeros((self.k, 2), dtype=np.float64)
+        for i, pe in enumerate(pes):          # (as BiquadPE._render fills them: 0.0 for a PE-valued parameter, never read)
+            rec[i]["freq"] = 0.0 if pe._freq_is_pe else float(pe._frequency)
+            rec[i]["q"] = 0.0 if pe._q_is_pe else float(pe._q)
+            rec[i]["gain_db"] = float(pe._gain_db)
+            rec[i]["mode"] = _MODE_INDEX[pe._mode]
+            gain_a = 10.0 ** (pe._gain_db / 40.0)
+            gains[i] = (gain_a, math.sqrt(gain_a))
+        self.params = _dev.upload_structs(rec)
+        self.gains = DeviceBuffer.from_host(gains)
+        self.state = None
+        self.ws = None
+
+    def reset(self):
+        super().reset()
+        if self.state is not None:
+            self.state.zero_()
+
+    def channels(self):
+        return self.children["source"].channels()
+
+    def render(self, start, n):
+        L = lib()
+        x = self.children["source"].render(start, n)
+        freq = self.children["frequency"].render(start, n) if "frequency" in self.children else None
+        q = self.children["q"].render(start, n) if "q" in self.children else None
+        ch = x.shape[2]
+        if self.state is None:
+            self.state = DeviceBuffer((self.k, ch, 4), np.float64, zero=True)
+        # enough rows to give every CU a workgroup: each row walked by one workgroup, one launch, the coefficients
+        # evaluated once (no workspace) instead of the segmented plan's reduce and apply
+        walk = self.k * ch >= BIQUAD_VAR_WALK_MIN_ROWS
+        need = 0 if walk else self.k * L.pgx_scan2_workspace_bytes(n, ch)
+        if need and (self.ws is None or self.ws.nbytes < need):
+            self.ws = DeviceBuffer((need,), np.uint8)
+        out = DeviceBuffer((self.k, n, ch), np.float32)
+        check(L.pgx_biquad_varying_bank(out.ptr, n * ch, x.ptr, getattr(x, "stride", n * ch), self.k, n, ch, self.sr,
+                                        self.params.ptr, self.gains.ptr, ptr(freq), getattr(freq, "stride", n),
+                                        ptr(q), getattr(q, "stride", n), self.state.ptr,
+                                        ptr(self.ws) if need else None), "pgx_biquad_varying_bank")
+        return out
+
+
 class _LadderNode(_Windowed, _Node):
     """Bank of LadderPEs.  The ladder kernel is latency-bound (two waves per CU, most of the chip idle) and its
     input, a bank of scalar oscillators, is a pure function of time plus a few carried numbers -- so while block k
@@ -1165,8 +1242,8 @@ class _Kind(NamedTuple):
     batchable: object            # (pe) -> bool
     extras: object               # (pe) -> what else goes into the key, or None
     children: tuple              # ((name the node knows the child by, attribute of the PE that holds it, present(pe)), ...)
-    node: type                   # node(pes, children); node(pes) for a class without children
-    min_voices: object = None    # () -> voices below which a tree that holds this class is not banked (None: MIN_VOICES)
+    node: object                 # node(pes, children); node(pes) for a class without children
+    min_voices: object = None    # (pe) -> voices below which a tree that holds this PE is not banked (None: MIN_VOICES)
 
 
 _ALWAYS = lambda pe: True
@@ -1176,6 +1253,16 @@ _SOURCE = ("source", "_source", _ALWAYS)
 def _osc_batchable(pe) -> bool:
     """Parameter PEs as (n, 1) streams only (what the kernel reads; the PE itself takes channel 0 of anything)."""
     return all(p.channel_count() == 1 for p in pe.inputs())
+
+
+def _biquad_swept(pe) -> bool:
+    """A BiquadPE whose cutoff or Q is a PE: per-sample coefficients (_BiquadVarNode)."""
+    return bool(pe._freq_is_pe or pe._q_is_pe)
+
+
+def _biquad_batchable(pe) -> bool:
+    """Constant coefficients, or parameter PEs that are (n, 1) streams: the rule of _osc_batchable."""
+    return all(p.channel_count() == 1 for p, is_pe in ((pe._frequency, pe._freq_is_pe), (pe._q, pe._q_is_pe)) if is_pe)
 
 
 def _transform_codes(pe):
@@ -1200,10 +1287,16 @@ _KINDS = (
     _Kind(AnalogOscPE, "analog_osc", _osc_batchable,
           lambda pe: (pe._waveform, pe._channels, _is_pe(pe._frequency), _is_pe(pe._duty_cycle)),
           (("frequency", "_frequency", lambda pe: _is_pe(pe._frequency)),
-           ("duty", "_duty_cycle", lambda pe: _is_pe(pe._duty_cycle))), _AnalogOscNode, lambda: ANALOG_OSC_MIN_VOICES),
+           ("duty", "_duty_cycle", lambda pe: _is_pe(pe._duty_cycle))), _AnalogOscNode, lambda pe: ANALOG_OSC_MIN_VOICES),
     _Kind(TransformPE, "transform", lambda pe: _transform_codes(pe) is not None, lambda pe: (_transform_codes(pe),),
           (_SOURCE,), _TransformNode),
-    _Kind(BiquadPE, "biquad", lambda pe: not (pe._freq_is_pe or pe._q_is_pe), None, (_SOURCE,), _BiquadNode),
+    # (constant coefficients: _BiquadNode; a PE-driven cutoff or Q: _BiquadVarNode -- mode, gain_db and the scalar of the
+    # other parameter are per-voice data there, which parameters are PEs is part of the key)
+    _Kind(BiquadPE, lambda pe: "biquad_var" if _biquad_swept(pe) else "biquad", _biquad_batchable,
+          lambda pe: (pe._freq_is_pe, pe._q_is_pe) if _biquad_swept(pe) else (),
+          (_SOURCE, ("frequency", "_frequency", lambda pe: pe._freq_is_pe), ("q", "_q", lambda pe: pe._q_is_pe)),
+          lambda pes, children: (_BiquadVarNode if _biquad_swept(pes[0]) else _BiquadNode)(pes, children),
+          lambda pe: BIQUAD_VAR_MIN_VOICES if _biquad_swept(pe) else MIN_VOICES),
     _Kind(LadderPE, "ladder", lambda pe: not (pe._freq_is_pe or pe._res_is_pe or pe._drive_is_pe), None, (_SOURCE,),
           _LadderNode),
     _Kind(CombPE, "comb", lambda pe: not (pe._freq_is_pe or pe._fb_is_pe), None, (_SOURCE,), _CombNode),
@@ -1241,7 +1334,7 @@ def _signature(pe):
 def _min_voices(pe) -> int:
     """Voices from which trees like `pe` (batchable: _signature) are banked: the largest minimum of a class in the tree."""
     kind = _kind(pe)
-    need = kind.min_voices() if kind.min_voices is not None else MIN_VOICES
+    need = kind.min_voices(pe) if kind.min_voices is not None else MIN_VOICES
     for _, attribute, present in kind.children:
         if present(pe):
             need = max(need, _min_voices(getattr(pe, attribute)))

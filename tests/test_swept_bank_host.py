@@ -1,0 +1,114 @@
+"""Host: which swept-filter voices -- BiquadPE with a PE-driven cutoff and / or Q -- the voice bank takes
+(voice_bank._signature), what is key and what is per-voice data, and when try_build_bank declines."""
+
+import os
+import re
+
+import pygmu2_amd as pg
+from pygmu2_amd import device, voice_bank
+from pygmu2_amd.biquad_pe import BiquadMode
+from pygmu2_amd.transforms import Affine
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+FORMS = ("freq", "q", "both")
+
+
+def _cutoff(i=0, sweep=2500.0):
+    envelope = pg.AdsrGatedPE(pg.PeriodicGate(3.0 + 0.17 * i, 0.5), 0.01, 0.05, 0.6, 0.03)
+    return pg.TransformPE(envelope, func=Affine(sweep, 300.0 + 40.0 * i))
+
+
+def _q(i=0, **kw):
+    return pg.TransformPE(pg.SinePE(0.7 + 0.31 * i, **kw), func=Affine(1.2, 2.0))
+
+
+def _voice(i=0, form="both", channels=1, **kw):
+    return pg.BiquadPE(pg.BlitSawPE(109.37 * 2 ** (i / 12), channels=channels),
+                       frequency=_cutoff(i) if form in ("freq", "both") else 1500.0,
+                       q=_q(i) if form in ("q", "both") else 2.0, **kw)
+
+
+def _constant(i=0):
+    return pg.BiquadPE(pg.BlitSawPE(109.37 * 2 ** (i / 12)), frequency=1500.0, q=2.0)
+
+
+def test_the_three_forms_have_signatures_of_their_own():
+    pg.set_sample_rate(48000)
+    sigs = {form: voice_bank._signature(_voice(0, form)) for form in FORMS}
+    assert all(s is not None for s in sigs.values())
+    assert len(set(sigs.values())) == 3
+    constant = voice_bank._signature(_constant())
+    assert constant == ("biquad", ("blitsaw", 1))                     # (unchanged)
+    assert constant not in sigs.values()
+    saw, cutoff, q = (voice_bank._signature(pe) for pe in (pg.BlitSawPE(110.0), _cutoff(), _q()))
+    assert sigs["freq"] == ("biquad_var", True, False, saw, cutoff)
+    assert sigs["q"] == ("biquad_var", False, True, saw, q)
+    assert sigs["both"] == ("biquad_var", True, True, saw, cutoff, q)
+    assert voice_bank._signature(_voice(0, "both", channels=2)) != sigs["both"]
+
+
+def test_per_voice_data_is_not_part_of_the_key():
+    pg.set_sample_rate(48000)
+    sig = voice_bank._signature
+    for form in FORMS:
+        want = sig(_voice(0, form))
+        for i, mode in enumerate(BiquadMode):
+            assert sig(_voice(i, form, mode=mode, gain_db=3.0 * (i % 3) - 3.0)) == want
+    assert sig(pg.BiquadPE(pg.BlitSawPE(110.0), frequency=_cutoff(2, sweep=900.0), q=0.8)) == sig(_voice(0, "freq"))
+    assert sig(pg.BiquadPE(pg.BlitSawPE(110.0), frequency=700.0, q=_q(3))) == sig(_voice(0, "q"))
+
+
+def test_what_is_not_batchable():
+    pg.set_sample_rate(48000)
+    saw = lambda: pg.BlitSawPE(110.0)
+    assert voice_bank._signature(pg.BiquadPE(saw(), frequency=1500.0, q=_q(channels=2))) is None      # a stereo modulator
+    assert voice_bank._signature(pg.BiquadPE(saw(), frequency=pg.SinePE(2.0, channels=2), q=2.0)) is None
+    host = pg.TransformPE(pg.SinePE(1.0), func=lambda v: 1000.0 + 400.0 * v)                            # a host callable
+    assert voice_bank._signature(pg.BiquadPE(saw(), frequency=host, q=2.0)) is None
+    assert voice_bank._signature(pg.BiquadPE(saw(), frequency=1500.0, q=host)) is None
+    # the other filters with PE parameters stay unbatched (tests/test_host_logic.py)
+    comb = lambda i: pg.CombPE(pg.BlitSawPE(frequency=110.0 + i), frequency=220.0 + i, feedback=0.5)
+    assert voice_bank._signature(comb(0)) == ("comb", ("blitsaw", 1))
+    assert voice_bank._signature(pg.CombPE(saw(), frequency=pg.SinePE(2.0), feedback=0.5)) is None
+    assert voice_bank._signature(pg.CombPE(saw(), frequency=220.0, feedback=pg.SinePE(2.0))) is None
+    assert voice_bank._signature(pg.LadderPE(saw(), frequency=_cutoff(), resonance=0.3)) is None
+    assert voice_bank._signature(pg.SVFilterPE(saw(), frequency=_cutoff(), q=2.0)) is None
+
+
+def test_the_minimum_is_the_measured_one_and_a_switch(monkeypatch):
+    pg.set_sample_rate(48000)
+    assert voice_bank.BIQUAD_VAR_MIN_VOICES >= voice_bank.MIN_VOICES
+    assert voice_bank._min_voices(_voice()) == voice_bank.BIQUAD_VAR_MIN_VOICES
+    assert voice_bank._min_voices(pg.GainPE(_voice(), 0.5)) == voice_bank.BIQUAD_VAR_MIN_VOICES
+    assert voice_bank._min_voices(_constant()) == voice_bank.MIN_VOICES
+    monkeypatch.setattr(voice_bank, "BIQUAD_VAR_MIN_VOICES", 7)
+    assert voice_bank._min_voices(_voice()) == 7
+    assert voice_bank.try_build_bank([_voice(i) for i in range(6)]) is None
+    assert voice_bank.try_build_bank([_voice(i) for i in range(voice_bank.MIN_VOICES - 1)]) is None
+
+
+def test_a_mixed_list_is_declined(monkeypatch):
+    pg.set_sample_rate(48000)
+    monkeypatch.setattr(voice_bank, "BIQUAD_VAR_MIN_VOICES", voice_bank.MIN_VOICES)
+    assert voice_bank.try_build_bank([_voice(i, "freq" if i == 2 else "both") for i in range(5)]) is None
+    assert voice_bank.try_build_bank([_constant(i) if i == 2 else _voice(i, "freq") for i in range(5)]) is None
+    shared = _q()
+    voices = [pg.BiquadPE(pg.BlitSawPE(110.0 + i), frequency=1500.0, q=shared) for i in range(5)]
+    assert voice_bank.try_build_bank(voices) is None                                 # a modulator shared between voices
+
+
+def test_the_node_is_no_constant_biquad_node():
+    assert not issubclass(voice_bank._BiquadVarNode, voice_bank._BiquadNode)
+    assert voice_bank._BiquadVarNode._STATE == ("state",)
+
+
+def test_abi_of_the_bank_entry():
+    text = open(os.path.join(ROOT, "include", "pygmu_hip.h")).read()
+    assert re.search(r"\bpgx_biquad_varying_bank\s*\(", text)
+    assert "pgx_biquad_varying_bank" in device.EXPORTED_SYMBOLS
+    lib = device.load_library()
+    assert hasattr(lib, "pgx_biquad_varying_bank")
+    # the bank's workspace is sized from the single entry's: a block of up to two tiles needs none, three tiles three maps
+    assert lib.pgx_scan2_workspace_bytes(2048, 3) == 0
+    assert lib.pgx_scan2_workspace_bytes(2049, 2) == 2 * (4 + 3 * 6) * 8
+    assert lib.pgx_scan2_workspace_bytes(132_099, 1) == (4 + 65 * 6) * 8
