@@ -31,6 +31,9 @@
 #include <stddef.h>
 #include <stdint.h>
 
+/* PGX_HOST marks a pointer parameter that the call itself dereferences on the host. */
+#define PGX_HOST
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -46,10 +49,10 @@ typedef enum {
 /* ------------------------------------------------------------------ runtime */
 int pgx_abi_version(void);
 const char *pgx_last_error(void);
-int pgx_device_count(int *count);
+int pgx_device_count(PGX_HOST int *count);
 int pgx_init(int device);                 /* select device, create stream + pool; idempotent */
 int pgx_shutdown(void);                   /* sync, release pool, destroy stream              */
-int pgx_device_name(char *buf, size_t len);
+int pgx_device_name(PGX_HOST char *buf, size_t len);
 void *pgx_stream_handle(void);            /* hipStream_t of the library stream               */
 int pgx_stream_sync(void);
 /* Two independent sub-graphs of one block may overlap on the device:
@@ -75,7 +78,7 @@ int pgx_stream_fork_after(void *event);
 int pgx_stream_wait_detached(void);
 int pgx_stream_is_detached(void);
 
-int pgx_malloc(void **dptr, size_t bytes);      /* pooled (size-class free lists)           */
+int pgx_malloc(PGX_HOST void **dptr, size_t bytes);      /* pooled (size-class free lists)           */
 int pgx_free(void *dptr);                       /* returns the block to the pool            */
 int pgx_pool_trim(void);                        /* hipFree every cached block               */
 int pgx_memset(void *dptr, int byte_value, size_t bytes);
@@ -89,17 +92,17 @@ int pgx_memcpy_d2d(void *dst, const void *src, size_t bytes);
  *                   the library stream so far -- the next block renders while this one crosses PCIe
  *   pgx_d2h_wait    the host blocks until that copy has landed
  *   pgx_d2h_fence   the library stream waits for it instead (before `src` is recycled unread) */
-int pgx_host_malloc(void **hptr, size_t bytes);
+int pgx_host_malloc(PGX_HOST void **hptr, size_t bytes);
 int pgx_host_free(void *hptr);
-int pgx_d2h_begin(void *dst_host, const void *src, size_t bytes, int64_t *ticket);
+int pgx_d2h_begin(void *dst_host, const void *src, size_t bytes, PGX_HOST int64_t *ticket);
 int pgx_d2h_wait(int64_t ticket);
-int pgx_d2h_query(int64_t ticket, int *done);   /* *done = 1 once that copy has landed; never blocks */
+int pgx_d2h_query(int64_t ticket, PGX_HOST int *done);   /* *done = 1 once that copy has landed; never blocks */
 int pgx_d2h_fence(int64_t ticket);
 
-int pgx_event_create(void **event);
+int pgx_event_create(PGX_HOST void **event);
 int pgx_event_destroy(void *event);
 int pgx_event_record(void *event);              /* on the library stream */
-int pgx_event_elapsed_ms(void *start, void *stop, float *ms);   /* synchronises on stop */
+int pgx_event_elapsed_ms(void *start, void *stop, PGX_HOST float *ms);   /* synchronises on stop */
 
 /* Diagnostics: evaluate the library's float64 sine / cosine (the routine every oscillator and
  * coefficient kernel uses in place of np.sin / np.cos) on n device doubles. */
@@ -171,7 +174,7 @@ int pgx_gain_const(float *out, const float *in, int64_t n_elems, float gain);
 int pgx_gain_vec(float *out, const float *in, const float *gain, int64_t n, int channels,
                  int gain_channels /* 1 (broadcast) or == channels */);
 /* ins_host: HOST array of k device pointers, each n_elems floats. */
-int pgx_mix_n(float *out, const float *const *ins_host, int k, int64_t n_elems);
+int pgx_mix_n(float *out, PGX_HOST const float *const *ins_host, int k, int64_t n_elems);
 /* Sum of `batch` equally shaped voices stored [batch][n_elems] (stride in elements),
  * accumulated in float32 in voice order 0..batch-1 (== MixPE over the voices). */
 int pgx_mix_batch(float *out, const float *in, int64_t in_stride, int batch, int64_t n_elems);
@@ -225,7 +228,7 @@ int pgx_biquad_sine_set_runs(int min_chunks);
  * head + (g - 1) * run, each after `warm` chunks of warm-up.  Returns 1, or 0 (out untouched) when the single-launch
  * filter kernel would render the block; follows pgx_biquad_sine_set_runs.  Needs pgx_init (the plan is sized by the
  * device's resident waves). */
-int pgx_biquad_sine_runs_plan(int64_t n, int64_t settle_frames, int out[5]);
+int pgx_biquad_sine_runs_plan(int64_t n, int64_t settle_frames, PGX_HOST int out[5]);
 
 /* Time-varying coefficients: _compute_coefficients per sample (biquad_pe.py:217-335) +
  * the direct-form-I recurrence of _biquad_varying_numba (biquad_pe.py:35-62).
@@ -809,15 +812,15 @@ int pgx_convolve_fft(float *out, const float *x, int64_t n, int src_channels, co
 size_t pgx_comm_unique_id_bytes(void);
 int pgx_comm_unique_id(void *id_host, size_t len);
 int pgx_comm_init(int rank, int world, const void *id_host, size_t len);
-int pgx_comm_info(int *rank, int *world);        /* world == 0: no communicator */
+int pgx_comm_info(PGX_HOST int *rank, PGX_HOST int *world);        /* world == 0: no communicator */
 int pgx_comm_destroy(void);
 int pgx_comm_quiesce(int timeout_ms);
 int pgx_comm_abandoned(void);
 int pgx_comm_fold_check(int64_t word);
-int pgx_comm_stats(int64_t *issued, int64_t *checks, int64_t *hash);
-int pgx_allreduce_sum(float *out, const float *in, size_t n, int64_t *ticket);
+int pgx_comm_stats(PGX_HOST int64_t *issued, PGX_HOST int64_t *checks, PGX_HOST int64_t *hash);
+int pgx_allreduce_sum(float *out, const float *in, size_t n, PGX_HOST int64_t *ticket);
 int pgx_allreduce_wait(int64_t ticket);
-int pgx_allreduce_scalar_host(double *value_host, int op);
+int pgx_allreduce_scalar_host(PGX_HOST double *value_host, int op);
 
 /* ------------------------------------------------------------------ KarplusStrongPE / AnalogOscPE (pgx_sources.hip)
  * KarplusStrongPE._render (karplus_strong_pe.py:137-213): a one-period circular line of float32 noise (drawn and

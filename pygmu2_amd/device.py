@@ -15,6 +15,8 @@ import threading
 
 import numpy as np
 
+from . import _abi
+
 _PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 # PGX_LIB_PATH: load another build of the same library (kernel experiments under experiments/)
 LIB_PATH = os.environ.get("PGX_LIB_PATH") or os.path.join(_PKG_DIR, "libpygmu_hip.so")
@@ -27,228 +29,51 @@ c_float_p = C.POINTER(C.c_float)
 c_double_p = C.POINTER(C.c_double)
 c_i32_p = C.POINTER(C.c_int32)
 
-# (name, restype, argtypes).  Device pointers are passed as c_void_p integers.
-_P = C.c_void_p
-_I = C.c_int
-_L = C.c_int64
-_D = C.c_double
-_F = C.c_float
-_Z = C.c_size_t
-_U = C.c_uint64
+# include/pygmu_hip.h is the definition of the ABI; it is read once, here.  Device pointers are c_void_p integers, the
+# header's PGX_HOST pointers are typed.
+HEADER_PATH = os.path.join(os.path.dirname(_PKG_DIR), "include", "pygmu_hip.h")
+_ABI = _abi.load(HEADER_PATH)
 
-_SIGNATURES = [
-    ("pgx_abi_version", _I, []),
-    ("pgx_last_error", C.c_char_p, []),
-    ("pgx_device_count", _I, [C.POINTER(_I)]),
-    ("pgx_init", _I, [_I]),
-    ("pgx_shutdown", _I, []),
-    ("pgx_device_name", _I, [C.c_char_p, _Z]),
-    ("pgx_stream_handle", _P, []),
-    ("pgx_stream_sync", _I, []),
-    ("pgx_stream_fork", _I, []),
-    ("pgx_stream_select", _I, [_I]),
-    ("pgx_stream_join", _I, []),
-    ("pgx_stream_is_forked", _I, []),
-    ("pgx_stream_detach", _I, []),
-    ("pgx_stream_fork_after", _I, [_P]),
-    ("pgx_stream_wait_detached", _I, []),
-    ("pgx_stream_is_detached", _I, []),
-    ("pgx_malloc", _I, [C.POINTER(_P), _Z]),
-    ("pgx_free", _I, [_P]),
-    ("pgx_pool_trim", _I, []),
-    ("pgx_memset", _I, [_P, _I, _Z]),
-    ("pgx_memcpy_h2d", _I, [_P, _P, _Z]),
-    ("pgx_memcpy_d2h", _I, [_P, _P, _Z]),
-    ("pgx_memcpy_d2d", _I, [_P, _P, _Z]),
-    ("pgx_host_malloc", _I, [C.POINTER(_P), _Z]),
-    ("pgx_host_free", _I, [_P]),
-    ("pgx_d2h_begin", _I, [_P, _P, _Z, C.POINTER(_L)]),
-    ("pgx_d2h_wait", _I, [_L]),
-    ("pgx_d2h_query", _I, [_L, C.POINTER(_I)]),
-    ("pgx_d2h_fence", _I, [_L]),
-    ("pgx_event_create", _I, [C.POINTER(_P)]),
-    ("pgx_event_destroy", _I, [_P]),
-    ("pgx_event_record", _I, [_P]),
-    ("pgx_event_elapsed_ms", _I, [_P, _P, C.POINTER(_F)]),
-    ("pgx_selftest_sincos", _I, [_P, _P, _P, _L]),
-    ("pgx_selftest_tanh", _I, [_P, _P, _L]),
-    ("pgx_fill", _I, [_P, _L, _F]),
-    ("pgx_ramp", _I, [_P, _F, _F, _L, _I]),
-    ("pgx_ramp_blocks", _I, [_P, _L, _L, _I, _L]),
-    ("pgx_dirac", _I, [_P, _L, _L, _I]),
-    ("pgx_window_copy", _I, [_P, _L, _L, _I, _P, _L, _L, _I, _I]),
-    ("pgx_extract_channel", _I, [_P, _P, _L, _I, _I]),
-    ("pgx_sine_render", _I, [_P, _L, _I, _L, _L, _I, _D, _P]),
-    ("pgx_sine_gain_render", _I, [_P, _L, _I, _L, _L, _I, _D, _P, _F]),
-    ("pgx_sine_stateful", _I, [_P, _L, _I, _D, _P, _P, _P, _P, _P]),
-    ("pgx_gain_const", _I, [_P, _P, _L, _F]),
-    ("pgx_gain_vec", _I, [_P, _P, _P, _L, _I, _I]),
-    ("pgx_mix_n", _I, [_P, C.POINTER(_P), _I, _L]),
-    ("pgx_mix_batch", _I, [_P, _P, _L, _I, _L]),
-    ("pgx_gain_mix_batch", _I, [_P, _P, _L, _P, _L, _I, _L, _I, _I]),
-    ("pgx_biquad_workspace_bytes", _Z, [_I, _L, _I, _L]),
-    ("pgx_biquad_table_doubles", _Z, []),
-    ("pgx_biquad_tables", _I, [_P, _P, _I]),
-    ("pgx_biquad_const", _I, [_P, _L, _P, _L, _I, _L, _I, _P, _P, _L, _P, _P]),
-    ("pgx_biquad_sine_supported", _I, [_L, _L]),
-    ("pgx_biquad_sine", _I, [_P, _L, _L, _D, _D, _D, _D, _P, _P, _L, _P, _P]),
-    ("pgx_biquad_sine_set_runs", _I, [_I]),
-    ("pgx_biquad_sine_runs_plan", _I, [_L, _L, C.POINTER(_I)]),
-    ("pgx_biquad_varying", _I, [_P, _P, _L, _I, _D, _P, _P, _P, _D, _D, _P, _P]),
-    ("pgx_biquad_varying_bank", _I, [_P, _L, _P, _L, _I, _L, _I, _D, _P, _P, _P, _L, _P, _L, _P, _P]),
-    ("pgx_scan2_workspace_bytes", _Z, [_L, _I]),
-    ("pgx_convolve_fft_size", _L, [_L]),
-    ("pgx_convolve_fft_spectrum_bytes", _Z, [_L, _I]),
-    ("pgx_convolve_fft_workspace_bytes", _Z, [_L, _L, _I, _L]),
-    ("pgx_convolve_fft_prepare", _I, [_P, _P, _L, _I, _L]),
-    ("pgx_convolve_fft", _I, [_P, _P, _L, _I, _P, _L, _I, _I, _L, _P, _P, _I]),
-    ("pgx_channel_adapt", _I, [_P, _P, _L, _I, _I]),
-    ("pgx_pan", _I, [_P, _P, _L, _I, C.c_float, _P, _I]),
-    ("pgx_mono_mean", _I, [_P, _P, _L, _I]),
-    ("pgx_loop", _I, [_P, _P, _L, _L, _I, _L, _L, _L]),
-    ("pgx_window_workspace_bytes", _Z, [_L, _I, _L]),
-    ("pgx_window", _I, [_P, _P, _L, _I, _L, _I, _I, _P]),
-    ("pgx_dynamics", _I, [_P, _P, _P, _L, _I, _I, _P]),
-    ("pgx_gate_stateful", _I, [_P, _L, _D, _D, _D, _D, _P, _P, _P, _P]),
-    ("pgx_hold", _I, [_P, _P, _I, _P, _I, _L, _F, _P, _P]),
-    ("pgx_slew_scratch_bytes", _Z, [_L]),
-    ("pgx_slew", _I, [_P, _P, _I, _L, _I, _D, _D, _P, _P, _P]),
-    ("pgx_function_gen_pure", _I, [_P, _L, _L, _I, _I, _D, _D, _D]),
-    ("pgx_function_gen_stateful", _I, [_P, _L, _I, _I, _D, _D, _D, _D, _P, _P, _P, _P, _P]),
-    ("pgx_interp_lookup", _I, [_P, _P, _L, _L, _I, _L, _L, _D, _P, _I, _I, _D, _D]),
-    ("pgx_index_range", _I, [_P, _P, _L, _L]),
-    ("pgx_wavetable", _I, [_P, _P, _L, _P, _L, _L, _I, _I, _I, _I, _D, _D]),
-    ("pgx_wavetable_range", _I, [_P, _P, _L, _I, _I, _D, _D]),
-    ("pgx_timewarp_scan", _I, [_P, _P, _P, _P, _P, _L]),
-    ("pgx_timewarp", _I, [_P, _L, _P, _D, _D, _P, _L, _L, _I, _I, _I, _D, _I, _D]),
-    ("pgx_stream_range", _I, [_P, _I, _P, _L]),
-    ("pgx_piecewise", _I, [_P, _L, _L, _I, _P, _P, _I, _I, _I, _I]),
-    ("pgx_f32_to_pcm16", _I, [_P, _P, _L]),
-    ("pgx_pcm16_to_f32", _I, [_P, _P, _L]),
-    ("pgx_svf", _I, [_P, _P, _L, _I, _D, _P, _P, _P, _D, _P, _P, _P]),
-    ("pgx_envelope_scratch_bytes", _Z, [_L, _I]),
-    ("pgx_envelope", _I, [_P, _P, _L, _I, _D, _D, _I, _I, _L, _P, _P]),
-    ("pgx_transform", _I, [_P, _P, _L, _P, _I]),
-    ("pgx_transform_bank", _I, [_P, _P, _L, _I, _P, _I]),
-    ("pgx_tuning", _I, [_P, _P, _L, _P, _I, _P, _P]),
-    ("pgx_selftest_tuning", _I, [_P, _P, _L, _I, _P, _P]),
-    ("pgx_blitsaw", _I, [_P, _L, _I, _L, _I, _D, _P, _P, _L, _P, _L, _P, _L, _P, _P, _P]),
-    ("pgx_blitsaw_workspace_bytes", _Z, [_I, _L, _I]),
-    ("pgx_supersaw_sum", _I, [_P, _L, _I, _I, _L, _I, _P, _P, _P, _L]),
-    ("pgx_blitsaw_biquad_bank", _I, [_P, _L, _I, _L, _D, _P, _P, _P, _P]),
-    ("pgx_blitsaw_biquad_wide", _I, [_P, _L, _I, _L, _P, _P, _P, _P, _P, _P, _L]),
-    ("pgx_blitsaw_biquad_wide_segments", _I, [_I, _L, _L]),
-    ("pgx_blitsaw_biquad_wide_seg", _I, [_P, _L, _I, _L, _P, _P, _P, _P, _P, _P, _P, _P, _L, _L]),
-    ("pgx_voice_tiles_max_warm", _L, []),
-    ("pgx_voice_tiles_table_bytes", _Z, [_I]),
-    ("pgx_voice_tiles_tables", _I, [_P, _P, _P, _P, _I]),
-    ("pgx_voice_tiles_workspace_bytes", _Z, [_I, _L, _L]),
-    ("pgx_voice_tiles_entries", _I, [_P, _I, _I, _L, _P, _P, _L, _L]),
-    ("pgx_voice_tiles", _I, [_P, _I, _L, _P, _P, _P, _P, _P, _P, _L, _L, _P, _I, _I]),
-    ("pgx_supersaw_bank", _I, [_P, _L, _I, _I, _L, _I, _D, _P, _P, _P]),
-    ("pgx_supersaw_bank_segments", _I, [_I, _L]),
-    ("pgx_supersaw_bank_seg", _I, [_P, _L, _I, _I, _L, _I, _D, _P, _P, _P, _P, _P]),
-    ("pgx_supersaw_bank_table_bytes", _Z, [_I, _I]),
-    ("pgx_supersaw_bank_tables", _I, [_P, _I, _I, _D, _P]),
-    ("pgx_supersaw_wide_table_bytes", _Z, [_I, _I]),
-    ("pgx_supersaw_wide_tables", _I, [_P, _I, _I, _D, _P]),
-    ("pgx_supersaw_wide_segments", _I, [_I, _I, _L]),
-    ("pgx_supersaw_wide", _I, [_P, _L, _I, _I, _L, _I, _P, _P, _P, _P]),
-    ("pgx_ladder", _I, [_P, _L, _P, _L, _I, _L, _I, _D, _P, _P, _P, _P, _P, _L, _L, _P]),
-    ("pgx_ladder_workspace_bytes", _Z, [_I, _L, _I, _L]),
-    ("pgx_comb", _I, [_P, _L, _P, _L, _I, _L, _I, _D, _P, _I, _I, _P, _P, _D, _L, _P, _L, _L, _I, _P, _P]),
-    ("pgx_comb_workspace_bytes", _Z, [_I, _L, _I, _I, _I]),
-    ("pgx_periodic_gate", _I, [_P, _L, _I, _L, _L, _P]),
-    ("pgx_periodic_trigger", _I, [_P, _L, _L, _L, _L, _F]),
-    ("pgx_adsr_workspace_bytes", _Z, [_I, _L]),
-    ("pgx_adsr_gated", _I, [_P, _L, _P, _L, _I, _L, _P, _P, _P]),
-    ("pgx_adsr_gated_periodic", _I, [_P, _L, _I, _L, _L, _P, _P, _P, _P, _I]),
-    ("pgx_adsr_gated_periodic_to", _I, [_P, _L, _I, _L, _L, _P, _P, _P, _P, _P, _I]),
-    ("pgx_adsr_triggered", _I, [_P, _L, _P, _L, _I, _L, _L, _P, _P, _P]),
-    ("pgx_convolve_workspace_bytes", _Z, [_L, _L, _I]),
-    ("pgx_convolve", _I, [_P, _P, _L, _I, _P, _L, _I, _I, _P, _P]),
-    ("pgx_comm_unique_id_bytes", _Z, []),
-    ("pgx_comm_unique_id", _I, [_P, _Z]),
-    ("pgx_comm_init", _I, [_I, _I, _P, _Z]),
-    ("pgx_comm_info", _I, [C.POINTER(_I), C.POINTER(_I)]),
-    ("pgx_comm_destroy", _I, []),
-    ("pgx_comm_quiesce", _I, [_I]),
-    ("pgx_comm_abandoned", _I, []),
-    ("pgx_comm_fold_check", _I, [_L]),
-    ("pgx_comm_stats", _I, [C.POINTER(_L), C.POINTER(_L), C.POINTER(_L)]),
-    ("pgx_allreduce_sum", _I, [_P, _P, _Z, C.POINTER(_L)]),
-    ("pgx_allreduce_wait", _I, [_L]),
-    ("pgx_allreduce_scalar_host", _I, [C.POINTER(_D), _I]),
-    ("pgx_karplus_strong", _I, [_P, _L, _I, _L, _L, _I, _P, _P, _P, _I]),
-    ("pgx_karplus_score", _I, [_P, _I, _P, _I, _I, _I, _I]),
-    ("pgx_analog_osc_workspace_bytes", _Z, [_L]),
-    ("pgx_analog_osc_pure", _I, [_P, _L, _L, _I, _D, _I, _D, _D, _P]),
-    ("pgx_analog_osc_stateful", _I, [_P, _L, _I, _D, _I, _D, _D, _P, _P, _I, _P, _P]),
-    ("pgx_analog_osc_bank_workspace_bytes", _Z, [_L, _I]),
-    ("pgx_analog_osc_bank", _I, [_P, _L, _I, _L, _L, _I, _D, _I, _P, _P, _L, _P, _L, _I, _I, _P, _P]),
-    ("pgx_noise_skip_table", _I, [_P]),
-    ("pgx_noise_white", _I, [_P, _L, _I, _L, _U, _P]),
-    ("pgx_noise_pink", _I, [_P, _L, _I, _L, _U, _P, _P]),
-    ("pgx_noise_brown", _I, [_P, _L, _I, _L, _U, _P, _P]),
-    ("pgx_dft_max_length", _L, []),
-    ("pgx_dft_plan_bytes", _Z, [_L]),
-    ("pgx_dft_workspace_bytes", _Z, [_L, _I]),
-    ("pgx_dft_plan", _I, [_P, _L]),
-    ("pgx_dft_c2c", _I, [_P, _P, _L, _I, _I, _P, _P]),
-    ("pgx_tralfam_workspace_bytes", _Z, [_L, _I]),
-    ("pgx_tralfam", _I, [_P, _P, _L, _I, _P, _D, _P, _P]),
-    ("pgx_score_mix", _I, [_P, _L, _I, _P, _L, _P, _P, _L]),
-    ("pgx_restart_plan", _I, [_P, _P, _P, _I, _L]),
-    ("pgx_restart_gather", _I, [_P, _L, _I, _P, _I, _P, _L, _P, _L, _P, _I]),
-    ("pgx_reverse_echo_workspace_bytes", _Z, [_L, _I]),
-    ("pgx_reverse_echo", _I, [_P, _P, _L, _I, _D, _D, _P, _D, _P, _D, _P, _D, _P, _L, _P, _P, _P, _L, _P, _L, _P]),
-]
-
+# (name, restype, argtypes)
+_SIGNATURES = [(name, res, args) for name, (res, args) in _ABI.functions.items()]
 EXPORTED_SYMBOLS = [s[0] for s in _SIGNATURES]
 
-# numpy mirrors of the parameter structs in include/pygmu_hip.h
-SINE_PARAMS = np.dtype([("w", "<f8"), ("amp", "<f8"), ("phase0", "<f8")])
-SINE_STATEFUL_PARAMS = np.dtype([("freq", "<f8"), ("amp", "<f8"), ("phase", "<f8"),
-                                 ("phase_is_stream", "<i4"), ("pad", "<i4")])
-BIQUAD_VAR_PARAMS = np.dtype([("freq", "<f8"), ("q", "<f8"), ("gain_db", "<f8"),
-                              ("mode", "<i4"), ("pad", "<i4")])
-DYNAMICS_PARAMS = np.dtype([("mode", "<i4"), ("soft", "<i4"), ("stereo_link", "<i4"), ("wide_makeup", "<i4"),
-                            ("threshold", "<f4"), ("slope", "<f4"), ("neg_slope", "<f4"), ("half_knee", "<f4"),
-                            ("two_knee", "<f4"), ("knee", "<f4"), ("knee_lo", "<f4"), ("knee_hi", "<f4"),
-                            ("gate_range", "<f4"), ("makeup", "<f4"), ("gate_range_d", "<f8"), ("makeup_d", "<f8")])
-BLITSAW_PARAMS = np.dtype([("freq", "<f8"), ("amp", "<f8"), ("leak", "<f8"), ("m", "<f8")])
-LADDER_PARAMS = np.dtype([("freq", "<f8"), ("resonance", "<f8"), ("drive", "<f8"),
-                          ("passband_gain", "<f8"), ("oversample", "<i4"), ("mode", "<i4")])
-COMB_PARAMS = np.dtype([("feedback", "<f8"), ("delay", "<i4"), ("buffer_len", "<i4")])
-TRANSFORM_OP = np.dtype([("code", "<i4"), ("pad", "<i4"), ("p0", "<f8"), ("p1", "<f8")])
-TUNING_OP = np.dtype([("code", "<i4"), ("tuning", "<i4"), ("p0", "<f8"), ("p1", "<f8")])
-TUNING_RECORD = np.dtype([("reference_pitch", "<f8"), ("reference_freq", "<f8"), ("divisions", "<f8"),
-                          ("table_offset", "<i8"), ("num_notes", "<i4"), ("pad", "<i4")])
-GATE_PARAMS = np.dtype([("dt", "<f8"), ("phase", "<f8"), ("duty", "<f8")])
-OSC_PARAMS = np.dtype([("freq", "<f8"), ("duty", "<f8")])
-KS_PARAMS = np.dtype([("line_offset", "<i8"), ("n", "<i4"), ("two_phase", "<i4"), ("switch_at", "<i8"),
-                      ("rho", "<f4"), ("rho_damping", "<f4"), ("c", "<f4"), ("pad", "<f4")])
-KS_STATE = np.dtype([("r", "<i4"), ("ap_in", "<f4"), ("ap_out", "<f4"), ("pad", "<i4")])
-KS_NOTE = np.dtype([("params", "<u8"), ("line", "<u8"), ("state", "<u8"), ("start", "<i8"), ("frames", "<i8"),
-                    ("dst", "<i8")])
-SCORE_INLINE = 16          # PGX_SCORE_INLINE: tables of at most this many entries travel in the kernel arguments
-SCORE_SEG = np.dtype([("data", "<u8"), ("first", "<i8"), ("frames", "<i8")])
-RESTART_TILE = 2048                 # PGX_RESTART_TILE: frames per tile of pgx_restart_plan / pgx_restart_gather
-RESTART_MAX_SEGMENTS = 1024         # PGX_RESTART_MAX_SEGMENTS: workgroups per launch at most
-RESTART_WORKSPACE_INT64 = 4 * RESTART_MAX_SEGMENTS
-RESTART_TAKE = np.dtype([("ptr", "<u8"), ("first", "<i8"), ("len", "<i8")])
-REVERSE_ECHO_MIN_BLOCK = 64         # PGX_REVERSE_ECHO_MIN_BLOCK: frames of the shortest echo block
-REVERSE_ECHO_MAX_FEEDBACK = 0.995   # PGX_REVERSE_ECHO_MAX_FEEDBACK
-REVERSE_ECHO_MIN_RATIO = 0.001      # PGX_REVERSE_ECHO_MIN_RATIO
-REVERSE_ECHO_UNITY_BAND = 1e-4      # PGX_REVERSE_ECHO_UNITY_BAND: |ratio - 1| below it bypasses the pitch shifter
-REVERSE_ECHO_STATE = np.dtype([("smoothed", "<f8"), ("read_pos", "<f8"), ("write_idx", "<i8"), ("read_idx", "<i8"),
-                               ("current_block", "<i8"), ("prev_len", "<i8"), ("pitch_write_pos", "<i8"),
-                               ("reverse", "<i4"), ("current_is_a", "<i4"), ("pitch_parity", "<i4"), ("pad", "<i4")])
-NOISE_PARAMS = np.dtype([("state_hi", "<u8"), ("state_lo", "<u8"), ("inc_hi", "<u8"), ("inc_lo", "<u8"),
-                         ("consumed", "<i8"), ("scaled", "<i4"), ("span", "<f4"), ("min_value", "<f4"), ("pad", "<i4")])
-NOISE_STATE = np.dtype([("pink", "<f4", (7,)), ("brown", "<f4")])
-ADSR_PARAMS = np.dtype([("attack_dvdt", "<f8"), ("decay_dvdt", "<f8"), ("release_dvdt", "<f8"),
-                        ("sustain_level", "<f8"), ("sustain_samples", "<i8")])
+# the header's parameter structs as numpy dtypes
+SINE_PARAMS = _ABI.struct("pgx_sine_params")
+SINE_STATEFUL_PARAMS = _ABI.struct("pgx_sine_stateful_params")
+BIQUAD_VAR_PARAMS = _ABI.struct("pgx_biquad_var_params")
+DYNAMICS_PARAMS = _ABI.struct("pgx_dynamics_params")
+BLITSAW_PARAMS = _ABI.struct("pgx_blitsaw_params")
+LADDER_PARAMS = _ABI.struct("pgx_ladder_params")
+COMB_PARAMS = _ABI.struct("pgx_comb_params")
+TRANSFORM_OP = _ABI.struct("pgx_transform_op")
+TUNING_OP = _ABI.struct("pgx_tuning_op")
+TUNING_RECORD = _ABI.struct("pgx_tuning_record")
+GATE_PARAMS = _ABI.struct("pgx_gate_params")
+OSC_PARAMS = _ABI.struct("pgx_osc_params")
+KS_PARAMS = _ABI.struct("pgx_ks_params")
+KS_STATE = _ABI.struct("pgx_ks_state")
+KS_NOTE = _ABI.struct("pgx_ks_note")
+SCORE_SEG = _ABI.struct("pgx_score_seg")
+RESTART_TAKE = _ABI.struct("pgx_restart_take")
+REVERSE_ECHO_STATE = _ABI.struct("pgx_reverse_echo_state")
+NOISE_PARAMS = _ABI.struct("pgx_noise_params")
+NOISE_STATE = _ABI.struct("pgx_noise_state")
+ADSR_PARAMS = _ABI.struct("pgx_adsr_params")
+
+# and its constants
+ERR_INVALID = _ABI.constant("PGX_ERR_INVALID")
+ERR_NOMEM = _ABI.constant("PGX_ERR_NOMEM")
+CONTROL_WORKSPACE_DOUBLES = _ABI.constant("PGX_CONTROL_WORKSPACE_DOUBLES")
+TIMEWARP_WORKSPACE_DOUBLES = _ABI.constant("PGX_TIMEWARP_WORKSPACE_DOUBLES")
+SCORE_INLINE = _ABI.constant("PGX_SCORE_INLINE")
+RESTART_TILE = _ABI.constant("PGX_RESTART_TILE")
+RESTART_MAX_SEGMENTS = _ABI.constant("PGX_RESTART_MAX_SEGMENTS")
+RESTART_WORKSPACE_INT64 = _ABI.constant("PGX_RESTART_WORKSPACE_INT64")
+REVERSE_ECHO_MIN_BLOCK = _ABI.constant("PGX_REVERSE_ECHO_MIN_BLOCK")
+REVERSE_ECHO_MAX_FEEDBACK = _ABI.constant("PGX_REVERSE_ECHO_MAX_FEEDBACK")
+REVERSE_ECHO_MIN_RATIO = _ABI.constant("PGX_REVERSE_ECHO_MIN_RATIO")
+REVERSE_ECHO_UNITY_BAND = _ABI.constant("PGX_REVERSE_ECHO_UNITY_BAND")
 
 
 def load_library():
@@ -285,9 +110,9 @@ def check(code: int, what: str = "") -> None:
         return
     msg = load_library().pgx_last_error().decode("utf-8", "replace")
     text = f"{what}: {msg}" if what else msg
-    if code == -1:
+    if code == ERR_INVALID:
         raise ValueError(text)
-    if code == -4:
+    if code == ERR_NOMEM:
         raise PgxOutOfMemory(f"{text} (pgx status {code})")
     raise PgxError(f"{text} (pgx status {code})")
 

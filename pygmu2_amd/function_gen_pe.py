@@ -14,13 +14,14 @@ from __future__ import annotations
 
 import numpy as np
 
+from . import device
 from ._kernels import DeviceBuffer, check, lib, new_output
 from .config import get_sample_rate
 from .extent import Extent
 from .processing_element import ProcessingElement
 from .snippet import Snippet
 
-_WORKSPACE_DOUBLES = 1040           # PGX_CONTROL_WORKSPACE_DOUBLES
+_WORKSPACE_DOUBLES = device.CONTROL_WORKSPACE_DOUBLES
 
 
 class FunctionGenPE(ProcessingElement):

@@ -14,12 +14,13 @@ from __future__ import annotations
 
 import numpy as np
 
+from . import device
 from ._kernels import DeviceBuffer, check, lib, new_output
 from .extent import Extent
 from .processing_element import ProcessingElement
 from .snippet import Snippet
 
-_WORKSPACE_DOUBLES = 1040           # PGX_CONTROL_WORKSPACE_DOUBLES
+_WORKSPACE_DOUBLES = device.CONTROL_WORKSPACE_DOUBLES
 
 
 class _HoldPE(ProcessingElement):

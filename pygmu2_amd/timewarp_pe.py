@@ -19,6 +19,7 @@ from __future__ import annotations
 
 import numpy as np
 
+from . import device
 from ._kernels import DeviceBuffer, check, lib, new_output
 from .delay_pe import InterpolationMode
 from .extent import Extent
@@ -29,7 +30,7 @@ from .snippet import Snippet
 # stream like any rendered rate -- so only rates that float32 holds exactly give the same output there
 NO_READBACK = True
 
-_WORKSPACE_DOUBLES = 768            # PGX_TIMEWARP_WORKSPACE_DOUBLES
+_WORKSPACE_DOUBLES = device.TIMEWARP_WORKSPACE_DOUBLES
 
 
 class TimeWarpPE(ProcessingElement):

@@ -435,17 +435,8 @@ def test_comb_and_small_oscillator_banks_are_batchable():
 
 def _raw_library():
     """The C-ABI library without a device: planning entry points only (nothing that launches)."""
-    import ctypes
-    from pygmu2_amd import build
-    lib = ctypes.CDLL(build.LIB_PATH)
-    lib.pgx_supersaw_wide_segments.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int64]
-    lib.pgx_supersaw_wide_table_bytes.argtypes = [ctypes.c_int, ctypes.c_int]
-    lib.pgx_supersaw_wide_table_bytes.restype = ctypes.c_size_t
-    lib.pgx_convolve_fft_size.argtypes = [ctypes.c_int64]
-    lib.pgx_convolve_fft_size.restype = ctypes.c_int64
-    lib.pgx_convolve_fft_workspace_bytes.argtypes = [ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int64]
-    lib.pgx_convolve_fft_workspace_bytes.restype = ctypes.c_size_t
-    return lib
+    from pygmu2_amd import device
+    return device.load_library()
 
 
 def test_segment_planner_of_the_wide_bank():

@@ -1,9 +1,7 @@
 """CPU: RandomSelectPE's surface against what the fixture records of the reference (tests/golden/random_select_cases.json),
 the order in which it consumes its random.Random, and the constants include/pygmu_hip.h shares with device.py."""
 
-import os
 import random
-import re
 
 import numpy as np
 import pytest
@@ -13,7 +11,6 @@ from pygmu2_amd import device, restart_bank
 import fixture_harness as H
 import random_select_oracle as R
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DATA, NPZ = H.load_cases("random_select")
 FACTS = DATA["facts"]
 
@@ -125,12 +122,10 @@ def test_the_composed_selector_draws_the_same_sequence():
 
 
 def test_header_constants_match_the_binding():
-    text = open(os.path.join(ROOT, "include", "pygmu_hip.h")).read()
-    tile = int(re.search(r"#define PGX_RESTART_TILE (\d+)", text).group(1))
-    segs = int(re.search(r"#define PGX_RESTART_MAX_SEGMENTS (\d+)", text).group(1))
-    assert re.search(r"#define PGX_RESTART_WORKSPACE_INT64 \(4 \* PGX_RESTART_MAX_SEGMENTS\)", text)
-    assert (tile, segs) == (device.RESTART_TILE, device.RESTART_MAX_SEGMENTS)
-    assert device.RESTART_WORKSPACE_INT64 == 4 * segs
+    header = device._ABI.constants
+    tile, segs = header["PGX_RESTART_TILE"], header["PGX_RESTART_MAX_SEGMENTS"]
+    assert (tile, segs) == (device.RESTART_TILE, device.RESTART_MAX_SEGMENTS) == (2048, 1024)
+    assert header["PGX_RESTART_WORKSPACE_INT64"] == device.RESTART_WORKSPACE_INT64 == 4 * segs == 4 * 1024
     assert device.RESTART_TAKE.itemsize == 24
 
 

@@ -3,9 +3,6 @@
 and the echo-block length of a scalar block_seconds are the reference's; the constants of include/pygmu_hip.h, of
 pygmu2_amd/device.py and of the class agree; pgx_reverse_echo refuses bad arguments before it looks for a device."""
 
-import os
-import re
-
 import numpy as np
 import pytest
 
@@ -15,7 +12,6 @@ from fixture_harness import load_cases, split_blocks
 from pygmu2_amd import device
 from pygmu2_amd.build import build
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CASES, NPZ = load_cases(RC.FAMILY)
 ALL = CASES["cases"]
 BY_NAME = {c["name"]: c for c in ALL}
@@ -114,22 +110,23 @@ def test_constructor_and_export():
 
 
 def test_constants_shared_with_the_header():
-    text = open(os.path.join(ROOT, "include", "pygmu_hip.h")).read()
-    defines = dict(re.findall(r"#define (PGX_REVERSE_ECHO_[A-Z_]+) (\S+)", text))
-    assert {k: float(v) for k, v in defines.items()} == {
+    defines = {k: v for k, v in device._ABI.constants.items() if k.startswith("PGX_REVERSE_ECHO_")}
+    assert defines == {
         "PGX_REVERSE_ECHO_MIN_BLOCK": device.REVERSE_ECHO_MIN_BLOCK,
         "PGX_REVERSE_ECHO_MAX_FEEDBACK": device.REVERSE_ECHO_MAX_FEEDBACK,
         "PGX_REVERSE_ECHO_MIN_RATIO": device.REVERSE_ECHO_MIN_RATIO,
         "PGX_REVERSE_ECHO_UNITY_BAND": device.REVERSE_ECHO_UNITY_BAND}
+    assert (device.REVERSE_ECHO_MIN_BLOCK, device.REVERSE_ECHO_MAX_FEEDBACK, device.REVERSE_ECHO_MIN_RATIO,
+            device.REVERSE_ECHO_UNITY_BAND) == (64, 0.995, 0.001, 1e-4)
+    assert type(device.REVERSE_ECHO_MIN_BLOCK) is int
     cls = pg.ReversePitchEchoPE
     assert (cls._MAX_DELAY_SECONDS, cls._MIN_BLOCK_SAMPLES, cls._MAX_FEEDBACK) == (10.0, 64, 0.995)
     # the record of the header, field by field
-    body = re.search(r"typedef struct \{([^}]*)\} pgx_reverse_echo_state;", text).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    fields = re.findall(r"(double|int64_t|int32_t)\s+(\w+);", body)
-    kinds = {"double": "<f8", "int64_t": "<i8", "int32_t": "<i4"}
-    assert [(name, kinds[kind]) for kind, name in fields] == \
-        [(name, device.REVERSE_ECHO_STATE.fields[name][0].str) for name in device.REVERSE_ECHO_STATE.names]
+    assert device.REVERSE_ECHO_STATE is device._ABI.struct("pgx_reverse_echo_state")
+    assert [(name, device.REVERSE_ECHO_STATE.fields[name][0].str) for name in device.REVERSE_ECHO_STATE.names] == \
+        [("smoothed", "<f8"), ("read_pos", "<f8"), ("write_idx", "<i8"), ("read_idx", "<i8"), ("current_block", "<i8"),
+         ("prev_len", "<i8"), ("pitch_write_pos", "<i8"), ("reverse", "<i4"), ("current_is_a", "<i4"),
+         ("pitch_parity", "<i4"), ("pad", "<i4")]
     assert device.REVERSE_ECHO_STATE.itemsize == 72
 
 

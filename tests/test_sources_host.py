@@ -1,7 +1,6 @@
 """CPU: KarplusStrongPE / AnalogOscPE without a GPU -- the restatement in sources_oracle.py against the reference's
 fixtures (tests/golden/sources*.{json,npz}), rho_for_decay_db, the classes' host-side contract, and the C ABI entries."""
 
-import os
 import re
 
 import numpy as np
@@ -12,7 +11,6 @@ from fixture_harness import load_cases, stored_blocks
 from pygmu2_amd import device, look_ahead, read_ahead
 from sources_oracle import AnalogOsc, KarplusStrong
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DATA, NPZ = load_cases("sources")
 CASES = DATA["cases"]
 
@@ -128,10 +126,9 @@ def test_analog_osc_contract():
 
 
 def test_abi_covers_new_entries():
-    text = open(os.path.join(ROOT, "include", "pygmu_hip.h")).read()
     names = ("pgx_karplus_strong", "pgx_analog_osc_workspace_bytes", "pgx_analog_osc_pure", "pgx_analog_osc_stateful")
     for name in names:
-        assert re.search(rf"\b{name}\s*\(", text), name
+        assert name in device._ABI.functions, name
         assert name in device.EXPORTED_SYMBOLS
     assert device.KS_PARAMS.itemsize == 40 and device.KS_STATE.itemsize == 16
     lib = device.load_library()

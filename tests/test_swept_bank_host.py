@@ -1,15 +1,11 @@
 """Host: which swept-filter voices -- BiquadPE with a PE-driven cutoff and / or Q -- the voice bank takes
 (voice_bank._signature), what is key and what is per-voice data, and when try_build_bank declines."""
 
-import os
-import re
-
 import pygmu2_amd as pg
 from pygmu2_amd import device, voice_bank
 from pygmu2_amd.biquad_pe import BiquadMode
 from pygmu2_amd.transforms import Affine
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FORMS = ("freq", "q", "both")
 
 
@@ -103,8 +99,7 @@ def test_the_node_is_no_constant_biquad_node():
 
 
 def test_abi_of_the_bank_entry():
-    text = open(os.path.join(ROOT, "include", "pygmu_hip.h")).read()
-    assert re.search(r"\bpgx_biquad_varying_bank\s*\(", text)
+    assert "pgx_biquad_varying_bank" in device._ABI.functions
     assert "pgx_biquad_varying_bank" in device.EXPORTED_SYMBOLS
     lib = device.load_library()
     assert hasattr(lib, "pgx_biquad_varying_bank")
