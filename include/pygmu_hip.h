@@ -229,6 +229,18 @@ int pgx_biquad_sine_set_runs(int min_chunks);
  * filter kernel would render the block; follows pgx_biquad_sine_set_runs.  Needs pgx_init (the plan is sized by the
  * device's resident waves). */
 int pgx_biquad_sine_runs_plan(int64_t n, int64_t settle_frames, PGX_HOST int out[5]);
+/* Deadline pacing of the wave-run kernel: every wave sets its issue priority once per chunk by how far it is behind
+ * the schedule the previous window's duration gives it (read on the device, no synchronisation), so that the waves of
+ * a SIMD end together.  It changes no sample.  A window is paced only when the runs-launch before it had the same plan
+ * and no other pgx_biquad_sine render lies between them: the first window of a stream, a window after a change of
+ * size and a window after a seek's render run unpaced.  0 off, 1 on (environment: PGX_SB_SINE_PACING), a negative
+ * value restores the default.  Returns the previous value. */
+int pgx_biquad_sine_set_pacing(int mode);
+/* What the last wave-run launch rendered with pacing on left on the device, after a synchronise of the library's
+ * stream (done here): out = {its launch id, the longest duration among its recording waves (one in 61) in ticks of
+ * 10 ns, the ticks per chunk (tau) it was given: 0 = it ran unpaced}; three zeros before the first such launch.  out is
+ * host memory. */
+int pgx_biquad_sine_pacing_info(int64_t out[3]);
 
 /* Time-varying coefficients: _compute_coefficients per sample (biquad_pe.py:217-335) +
  * the direct-form-I recurrence of _biquad_varying_numba (biquad_pe.py:35-62).

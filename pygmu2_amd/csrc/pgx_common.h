@@ -22,6 +22,9 @@ hipStream_t main_stream();   // the stream `stream()` returns outside a fork
 bool initialised();
 int device_index();
 
+// Frees the pacing words of the BiquadPE(SinePE) window kernel (pgx_scan.hip); pgx_shutdown calls it.
+void biquad_sine_pacing_release();
+
 }  // namespace pgx
 
 #define PGX_REQUIRE_INIT()                                                        \

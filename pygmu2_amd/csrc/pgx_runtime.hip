@@ -162,6 +162,7 @@ int pgx_shutdown(void) {
         return PGX_ERR_RUNTIME;                          // (pgx_last_error() still holds pgx_comm_destroy's message)
     }
     pgx_pool_trim();
+    pgx::biquad_sine_pacing_release();
     std::lock_guard<std::mutex> lock(r.mu);
     for (auto &kv : r.live) (void)hipFree(kv.first);   // parked blocks are still listed in `live`
     r.live.clear();

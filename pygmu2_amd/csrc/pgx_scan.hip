@@ -991,6 +991,10 @@ __device__ __forceinline__ double readlane63_f64(double v) {
 //   PGX_SB_RUNS_NO_STORE  the hot path's global stores compiled out: wrong output, the timing of everything else
 //   PGX_SB_RUNS_STAMPS    every wave records wall_clock64() (100 MHz) at entry, with its constants ready, after its
 //                         first stored chunk and at exit (pgx_biquad_sine_runs_stamps reads them)
+//   PGX_SB_RUNS_PACE_SHIFT=k  the pacing thresholds at -1, +1 and +3 times tau / 2^k instead of tau / 4
+#ifndef PGX_SB_RUNS_PACE_SHIFT
+#define PGX_SB_RUNS_PACE_SHIFT 2
+#endif
 typedef unsigned int runs_v4u __attribute__((ext_vector_type(4)));
 
 // stage_store for the runs kernel's full, aligned chunks: 16 consecutive frames per lane -> four coalesced 1 KB rows,
@@ -1019,6 +1023,40 @@ __device__ __forceinline__ void runs_store_chunk(float *lds, float *dst, int lan
     }
 }
 
+// Deadline pacing.  The SIMD issues by priority, then by age, so four resident waves of equal priority do not share it:
+// the first dispatched runs at the speed of its own dependent chains, the others in the gaps it leaves, the grid leaves
+// in four steps and the last quarter of a window's bytes is written by SIMDs that hold one or two latency-bound waves
+// (DESIGN section 7).  A paced wave reads the 100 MHz wall clock at entry and once per chunk and sets its issue priority
+// by how far it is behind `done x tau`, tau being the time per chunk the launch was given: ahead of schedule 0, on it 1,
+// behind 2, behind by most of a chunk 3.  The waves of a SIMD then advance together and end together.  A priority
+// changes no sample and makes no wave wait for another; who renders which chunk stays as it is.
+//
+// tau comes from the window before, on the device: at exit one wave in kPaceRecordEvery records (launch id << 32) | its ticks
+// since entry into words[0] by atomicMax -- a newer launch's value dominates any older one, so nothing is zeroed
+// between launches -- and the next launch reads the word in its prologue.  It takes it only under the id the host names
+// as the previous runs-launch of the same plan; then tau = ticks x per_chunk (factor / (run + warm)), otherwise 0: no
+// pacing, no clock read in the chunk loop and no change of priority.  Wave 0 leaves (id << 32) | tau in words[1] for
+// pgx_biquad_sine_pacing_info.  words == nullptr (pacing switched off): the kernel reads no clock at all.
+constexpr int kPaceRecordEvery = 61;     // a prime: the recording waves fall on every SIMD, CU and quarter of the dispatch
+struct RunsPace {
+    unsigned long long *words;
+    unsigned id, prev_id;
+    float per_chunk;
+};
+
+// lag: ticks behind schedule, tau: ticks per chunk; thresholds at -1/4, +1/4 and +3/4 tau.  The pacing state lives in
+// vector registers (the kernel has none of the scalar ones to spare) with the same value in every lane; the level goes
+// through readfirstlane, so the branches are scalar ones around an s_setprio each (it takes an immediate)
+__device__ __forceinline__ void runs_pace_priority(int lag, int tau) {
+    const int q = tau >> PGX_SB_RUNS_PACE_SHIFT;
+    switch (__builtin_amdgcn_readfirstlane((lag >= -q) + (lag >= q) + (lag >= 3 * q))) {
+    case 0: __builtin_amdgcn_s_setprio(0); break;
+    case 1: __builtin_amdgcn_s_setprio(1); break;
+    case 2: __builtin_amdgcn_s_setprio(2); break;
+    default: __builtin_amdgcn_s_setprio(3); break;
+    }
+}
+
 #ifdef PGX_SB_RUNS_STAMPS
 constexpr int kRunStampWaves = 4096;
 __device__ unsigned long long g_runs_stamps[2][kRunStampWaves][4];
@@ -1027,7 +1065,7 @@ __device__ unsigned long long g_runs_stamps[2][kRunStampWaves][4];
 __global__ void __launch_bounds__(kRunBlock, PGX_SB_RUNS_WAVES)
 k_biquad_sine_runs(float *__restrict__ out, int64_t n, const double *__restrict__ coef,
                    const double *__restrict__ tables, double *state, int run, int head, int tail, int warm, int waves,
-                   SbRuns sine
+                   SbRuns sine, RunsPace pace
 #ifdef PGX_SB_RUNS_STAMPS
                    , int stamp_slot
 #endif
@@ -1044,6 +1082,14 @@ k_biquad_sine_runs(float *__restrict__ out, int64_t n, const double *__restrict_
     __syncthreads();
     const int g = blockIdx.x * (kRunBlock / 64) + wave;
     if (g >= waves) return;
+    // pacing: the entry clock, and the previous window's word on its way together with the table loads below
+    unsigned pace_t0 = 0;
+    unsigned long long pace_prev = 0;
+    if (pace.words) {
+        pace_t0 = (unsigned)wall_clock64();
+        if (pace.prev_id) pace_prev = __hip_atomic_load(pace.words, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    asm volatile("" : "+v"(pace_t0));                          // kept in a vector register, as all pacing state is
 
     float *wlds = stage_lds + wave * kStageWords;
     const bool io_aligned = aligned16(out);
@@ -1063,6 +1109,12 @@ k_biquad_sine_runs(float *__restrict__ out, int64_t n, const double *__restrict_
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::"v"(mlane.a), "v"(m16.a), "v"(m32.a), "v"(pwave.a), "v"(b0) : "memory");
     stamp[1] = wall_clock64();
 #endif
+    // ticks per chunk, or 0: not paced (no history under the id the host expects).  Below 2^24, 0.17 s per chunk
+    int pace_tau = 0;
+    if (pace.prev_id && (unsigned)(pace_prev >> 32) == pace.prev_id)
+        pace_tau = (int)fminf((float)(unsigned)pace_prev * pace.per_chunk, 16777216.0f);
+    unsigned pace_due = pace_t0;                               // the clock at which the current chunk is due to begin
+    asm volatile("" : "+v"(pace_tau), "+v"(pace_due));
 
     // renders the chunks [cb, ce) after `warm` chunks of warm-up (from the carried state at chunk 0).  Called once per
     // range, not from a loop over the ranges: the sine's constants are then not hoisted into registers for all of it
@@ -1084,6 +1136,12 @@ k_biquad_sine_runs(float *__restrict__ out, int64_t n, const double *__restrict_
         }
 #pragma nounroll
         for (; c < ce; ++c) {
+            // the clock is read here, where no LDS access is outstanding: it returns on the counter LDS reads return
+            // on, and a wait for it further down would hold the pass-2 row reads back
+            if (__builtin_amdgcn_readfirstlane(pace_tau)) {
+                runs_pace_priority((int)((unsigned)wall_clock64() - pace_due), pace_tau);
+                pace_due += (unsigned)pace_tau;
+            }
             float xf[kBqT];
             runs_sine16(sine, sn, cs, xf);
             // zero-state response of the lane's 16 frames
@@ -1151,12 +1209,13 @@ k_biquad_sine_runs(float *__restrict__ out, int64_t n, const double *__restrict_
         }
     };
     // the chunks of this wave, and for wave 0 the tail
-    if (g == 0) {
-        render(0, head < chunks ? head : chunks);
-        render(tail_start, chunks);
-    } else {
-        const int64_t cb = head + (int64_t)(g - 1) * run;
-        render(cb, cb + run < tail_start ? cb + run : tail_start);
+    // (two copies of the loop, not three: each keeps its xf[] in registers only while the three do not outgrow the
+    // compiler's budget for such arrays, and with the pacing code in the loop a third copy's went to scratch)
+    {
+        const int64_t cb = g == 0 ? 0 : head + (int64_t)(g - 1) * run;
+        const int64_t ce = g == 0 ? (head < chunks ? head : chunks) : (cb + run < tail_start ? cb + run : tail_start);
+        render(cb, ce);
+        if (g == 0) render(tail_start, chunks);
     }
 #ifdef PGX_SB_RUNS_STAMPS
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1164,6 +1223,16 @@ k_biquad_sine_runs(float *__restrict__ out, int64_t n, const double *__restrict_
     if (lane == 0 && g < kRunStampWaves)
         for (int k = 0; k < 4; ++k) g_runs_stamps[stamp_slot & 1][g][k] = stamp[k];
 #endif
+    // this wave's ticks for the next window's tau: fire and forget, nothing waits for the atomic.  One wave in
+    // kPaceRecordEvery records: atomics on one address are served one after the other, about 11 ns each, and with every
+    // wave of a 16 M-frame window recording the kernel ended 36 us later (52.8 us against 16.2 us)
+    if (pace.words && g % kPaceRecordEvery == 0) {
+        const unsigned long long ticks = (unsigned)wall_clock64() - pace_t0;
+        if (lane == 0) {
+            atomicMax(pace.words, ((unsigned long long)pace.id << 32) | ticks);
+            if (g == 0) pace.words[1] = ((unsigned long long)pace.id << 32) | (unsigned)pace_tau;
+        }
+    }
 }
 
 struct BqPlan {
@@ -4499,6 +4568,46 @@ int pgx_biquad_sine_runs_plan(int64_t n, int64_t settle_frames, int out[5]) {
     return 1;
 }
 
+// Deadline pacing of the wave runs (RunsPace).  PGX_SB_SINE_PACING=0 / 1 replaces the default,
+// pgx_biquad_sine_set_pacing overrides it; PGX_SB_SINE_PACE_FACTOR replaces kPaceFactor (experiments).
+constexpr int kPaceDefault = 1;
+constexpr float kPaceFactor = 1.0f;      // tau = the previous window's longest wave / (run + warm) x this
+static int &runs_pacing() {
+    static int v = getenv("PGX_SB_SINE_PACING") ? (atoi(getenv("PGX_SB_SINE_PACING")) != 0) : kPaceDefault;
+    return v;
+}
+static float pace_factor() {
+    static const float f = getenv("PGX_SB_SINE_PACE_FACTOR") ? (float)atof(getenv("PGX_SB_SINE_PACE_FACTOR")) : kPaceFactor;
+    return f;
+}
+// the two device words of RunsPace (made on first use, released by pgx_shutdown), the id of the last runs-launch and
+// its plan: the next launch is paced by its duration only if it has the same plan and follows it directly
+static struct {
+    unsigned long long *words = nullptr;
+    unsigned next_id = 1, last_id = 0;
+    int run = 0, warm = 0, waves = 0;
+} g_pace;
+
+int pgx_biquad_sine_set_pacing(int mode) {
+    const int was = runs_pacing();
+    runs_pacing() = mode < 0 ? kPaceDefault : (mode != 0);
+    return was;
+}
+
+int pgx_biquad_sine_pacing_info(int64_t out[3]) {
+    PGX_REQUIRE_INIT();
+    PGX_CHECK_ARG(out, "pgx_biquad_sine_pacing_info: null output");
+    out[0] = out[1] = out[2] = 0;
+    if (!g_pace.words) return PGX_OK;
+    unsigned long long w[2];
+    PGX_HIP(hipMemcpyAsync(w, g_pace.words, sizeof(w), hipMemcpyDeviceToHost, pgx::stream()));
+    PGX_HIP(hipStreamSynchronize(pgx::stream()));
+    out[0] = (int64_t)(w[0] >> 32);
+    out[1] = (int64_t)(w[0] & 0xffffffffull);
+    out[2] = (w[1] >> 32) == (w[0] >> 32) ? (int64_t)(w[1] & 0xffffffffull) : 0;
+    return PGX_OK;
+}
+
 #ifdef PGX_SB_RUNS_STAMPS
 static int g_runs_stamp_launch = 0;
 // the stamps of the last two window launches, [2][4096][4] ticks of 10 ns; slot = launch number & 1.  Returns the
@@ -4572,16 +4681,42 @@ int pgx_biquad_sine(float *out, int64_t start, int64_t n, double sample_rate, do
         sine.start = start;
         sine.state_backup = state_backup;
         const int groups = (rp.waves + kRunBlock / 64 - 1) / (kRunBlock / 64);
+        RunsPace pace{nullptr, 0, 0, 0.0f};
+        if (runs_pacing()) {
+            if (!g_pace.words) {                               // first use: two zeroed words, in stream order
+                void *p = nullptr;
+                PGX_HIP(hipMalloc(&p, 2 * sizeof(unsigned long long)));
+                g_pace.words = (unsigned long long *)p;
+                PGX_HIP(hipMemsetAsync(p, 0, 2 * sizeof(unsigned long long), pgx::stream()));
+            }
+            pace.words = g_pace.words;
+            if (g_pace.next_id == 0) {                         // the ids wrap: start over, or no new id would dominate
+                PGX_HIP(hipMemsetAsync(g_pace.words, 0, 2 * sizeof(unsigned long long), pgx::stream()));
+                g_pace.next_id = 1;
+                g_pace.last_id = 0;
+            }
+            pace.id = g_pace.next_id++;
+            if (g_pace.last_id && g_pace.run == rp.run && g_pace.warm == rp.warm && g_pace.waves == rp.waves)
+                pace.prev_id = g_pace.last_id;
+            pace.per_chunk = pace_factor() / (float)(rp.run + rp.warm);
+            g_pace.last_id = pace.id;
+            g_pace.run = rp.run;
+            g_pace.warm = rp.warm;
+            g_pace.waves = rp.waves;
+        } else {
+            g_pace.last_id = 0;
+        }
 #ifdef PGX_SB_RUNS_STAMPS
         hipLaunchKernelGGL(k_biquad_sine_runs, dim3(groups), dim3(kRunBlock), 0, pgx::stream(), out, n, coef, tables,
-                           state, rp.run, rp.head, rp.tail, rp.warm, rp.waves, sine, g_runs_stamp_launch++);
+                           state, rp.run, rp.head, rp.tail, rp.warm, rp.waves, sine, pace, g_runs_stamp_launch++);
 #else
         hipLaunchKernelGGL(k_biquad_sine_runs, dim3(groups), dim3(kRunBlock), 0, pgx::stream(), out, n, coef, tables,
-                           state, rp.run, rp.head, rp.tail, rp.warm, rp.waves, sine);
+                           state, rp.run, rp.head, rp.tail, rp.warm, rp.waves, sine, pace);
 #endif
         PGX_LAUNCH_CHECK("k_biquad_sine_runs");
         return PGX_OK;
     }
+    g_pace.last_id = 0;                                        // a render between two windows: the next one runs unpaced
     SbSine sine = cached;
     sine.amp = amp;
     sine.phase0 = phase0;
@@ -5231,3 +5366,14 @@ int pgx_transform(float *out, const float *in, int64_t n_elems, const pgx_transf
 }
 
 }  // extern "C"
+
+namespace pgx {
+
+// pgx_shutdown, with the streams drained: the pacing words go, and with them the history a next pgx_init could not use
+void biquad_sine_pacing_release() {
+    if (g_pace.words) (void)hipFree(g_pace.words);
+    g_pace.words = nullptr;
+    g_pace.last_id = 0;
+}
+
+}  // namespace pgx

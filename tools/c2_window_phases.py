@@ -3,14 +3,16 @@
 
     time per launch = fixed cost + rounds x cost per round          (a round: one 1024-frame chunk per resident wave)
 
-for the default build, the build without the hot path's stores (PGX_SB_RUNS_NO_STORE, csrc/pgx_scan.hip) and the store,
-prologue and priority variants that were measured and not kept (experiments/c2_window_variants.patch), and from the
+for the default build with deadline pacing off and on (a switch of the library, not a build), the build without the hot
+path's stores (PGX_SB_RUNS_NO_STORE, csrc/pgx_scan.hip) and the store, prologue and priority variants that were measured
+and not kept (experiments/c2_window_variants.patch), and from the
 PGX_SB_RUNS_STAMPS build each wave's own clock: the prologue, the first chunk, the spread of the waves' exits and the idle
 time between one launch's last exit and the next one's first entry.
 
     python tools/c2_window_phases.py build [--patched] [--only a,b]  # no GPU needed: experiments/variants/c2w_<name>.so
     python tools/c2_window_phases.py run [--out DIR] [--passes N]   # GPU: three passes, variants interleaved, one process each
     python tools/c2_window_phases.py run --only default,plain_serial
+    python tools/c2_window_phases.py run --only default_unpaced,default_paced,stamps_unpaced,stamps_paced
 
 `build` compiles csrc/pgx_scan.hip (with --patched: a patched copy of it) once per variant and links it with the other
 objects of the last library build (pygmu2_amd/csrc/_obj).  `run` writes c2_window_phases.jsonl (raw rows) and
@@ -32,6 +34,18 @@ VARIANTS = {
     "default": [],
     "no_store": ["-DPGX_SB_RUNS_NO_STORE"],
     "stamps": ["-DPGX_SB_RUNS_STAMPS"],
+    "pace_eighths": ["-DPGX_SB_RUNS_PACE_SHIFT=3"],          # pacing thresholds at -1/8, +1/8, +3/8 tau
+    "pace_halves": ["-DPGX_SB_RUNS_PACE_SHIFT=1"],           # ... at -1/2, +1/2, +3/2 tau
+}
+# Deadline pacing is a switch of the library (pgx_biquad_sine_set_pacing, PGX_SB_SINE_PACING), not a build: name ->
+# (the build it runs, its environment).  `default` and `stamps` themselves run with the library's default.
+SWITCHED = {
+    "default_unpaced": ("default", {"PGX_SB_SINE_PACING": "0"}),
+    "default_paced": ("default", {"PGX_SB_SINE_PACING": "1"}),
+    "stamps_unpaced": ("stamps", {"PGX_SB_SINE_PACING": "0"}),
+    "stamps_paced": ("stamps", {"PGX_SB_SINE_PACING": "1"}),
+    "pace_eighths_paced": ("pace_eighths", {"PGX_SB_SINE_PACING": "1"}),
+    "pace_halves_paced": ("pace_halves", {"PGX_SB_SINE_PACING": "1"}),
 }
 # The variants that were measured and not kept live in experiments/c2_window_variants.patch (PGX_SB_RUNS_VARIANT: bit 0
 # write-through stores -- the one kept --, bit 1 a chunk's four LDS reads ahead of its four stores, bit 2 the per-lane
@@ -61,7 +75,7 @@ PATCHED = {
 
 
 def lib_of(name):
-    return os.path.join(VDIR, f"c2w_{name}.so")
+    return os.path.join(VDIR, f"c2w_{SWITCHED.get(name, (name,))[0]}.so")
 
 
 def build(only=None, patched=False):
@@ -132,6 +146,9 @@ def worker(stamps):
         device.synchronize()
         row = {"frames": frames, "rounds": run + warm, "run": run, "warm": warm, "waves": waves,
                "us": round(e1.elapsed_ms_since(e0) / launches * 1e3, 3)}
+        info = (C.c_int64 * 3)()                               # the last launch: its duration and its tau, in ticks
+        device.check(raw.pgx_biquad_sine_pacing_info(info))
+        row.update(pacing_ticks=info[1], pacing_tau=info[2])
         if stamps:
             buf = np.zeros((2, 4096, 4), dtype=np.uint64)
             count = raw.pgx_biquad_sine_runs_stamps(C.c_void_p(buf.ctypes.data))
@@ -146,7 +163,9 @@ def worker(stamps):
                        stamp_prologue_max_us=us((last[:, 1] - last[:, 0]).max()),
                        stamp_first_chunk_us=us(np.median(last[1:, 2] - last[1:, 1])),
                        stamp_exit_min_us=us(exits.min()), stamp_exit_median_us=us(np.median(exits)),
-                       stamp_exit_max_us=us(exits.max()),
+                       stamp_exit_max_us=us(exits.max()), stamp_exit_spread_us=us(exits.max() - exits.min()),
+                       # (the earliest exit is the last wave's, whose run is the remainder: shorter than the others')
+                       stamp_exit_p01_us=us(np.percentile(exits, 1)), stamp_exit_p99_us=us(np.percentile(exits, 99)),
                        stamp_idle_between_launches_us=us(last[:, 0].min() - prev[:, 3].max()),
                        stamp_start_to_start_us=us(last[:, 0].min() - prev[:, 0].min()))
         print(json.dumps(row), flush=True)
@@ -164,14 +183,15 @@ def fit(us_by_frames, rounds_by_frames, runs_by_frames):
 
 
 def run(out_dir, only, passes=3):
-    names = [n for n in list(VARIANTS) + list(PATCHED) if os.path.exists(lib_of(n)) and (not only or n in only)]
+    names = [n for n in list(VARIANTS) + list(SWITCHED) + list(PATCHED)
+             if os.path.exists(lib_of(n)) and (not only or n in only)]
     assert names, "no variant library: run `build` first"
     os.makedirs(out_dir, exist_ok=True)
     rows = []
     with open(os.path.join(out_dir, "c2_window_phases.jsonl"), "w") as raw:
         for p in range(passes):
             for name in names:
-                env = dict(os.environ, PGX_LIB_PATH=lib_of(name))
+                env = dict(os.environ, PGX_LIB_PATH=lib_of(name), **SWITCHED.get(name, (name, {}))[1])
                 if name.startswith("stamps") and p == 0:
                     env["C2W_DUMP_STAMPS"] = os.path.join(out_dir, f"c2_window_stamps_{name}")
                 cmd = [sys.executable, os.path.abspath(__file__), "worker"] + (["--stamps"] if name.startswith("stamps") else [])
