@@ -292,6 +292,23 @@ int pgx_svf(float *out, const float *in, int64_t n, int channels, double sample_
             const double *coef /* NULL, or {a00,a01,a10,a11,b0,b1,c0,c1,c2} evaluated by the host
                                   (constant frequency and q; freq and q must then be NULL) */,
             double *state /* [channels][2] */, void *workspace /* as for pgx_biquad_varying */);
+/* Bank of SVFilterPEs (voice_bank.py): pgx_svf with the voice in the grid.
+ * in / out: `batch` rows of n * channels float32, in_stride / out_stride elements apart (each >= n * channels);
+ * freq / q: NULL (voice v takes params[v].freq / params[v].q) or `batch` rows of n float32, freq_stride / q_stride apart (>= n);
+ * params: device [batch] (mode and the scalars are per voice);  gains: device [batch], A = 10^(gain_db/40), the number the host
+ *         passes pgx_svf by value, per voice;  coef: NULL, or device [batch][9], voice v's host-evaluated constants as pgx_svf
+ *         takes them (freq and q must then be NULL);  state: [batch][channels][2];
+ * workspace: batch * pgx_scan2_workspace_bytes(n, channels) bytes (voice v's slice starts at v times that), or NULL.
+ * With a workspace every voice is rendered by pgx_svf's own plan (the reduce and the apply launch, grid (segments, channels,
+ * batch)); without one, or for blocks of one or two tiles, one workgroup per (voice, channel) walks the block in ONE launch.
+ * Either way row v holds the float32 samples and the final {s0, s1} that pgx_svf(row v, ..., the same choice of workspace)
+ * gives, bit for bit.
+ * n <= 0 or batch <= 0: PGX_OK, nothing launched.  batch > 65535, a stride below its row, a null out / in / params / gains /
+ * state, coef together with freq or q: PGX_ERR_INVALID, nothing launched. */
+int pgx_svf_bank(float *out, int64_t out_stride, const float *in, int64_t in_stride, int batch, int64_t n, int channels,
+                 double sample_rate, const pgx_biquad_var_params *params, const double *gains,
+                 const float *freq, int64_t freq_stride, const float *q, int64_t q_stride, const double *coef,
+                 double *state, void *workspace);
 
 /* EnvelopePE._render (envelope_pe.py:128-206) on the (already look-ahead shifted) source block.
  * one_pole != 0: attack == release, scipy lfilter one-pole as a scan; else the attack/release
@@ -680,6 +697,13 @@ int pgx_periodic_gate(float *out, int64_t out_stride, int batch, int64_t start, 
                       const pgx_gate_params *params);
 int pgx_periodic_trigger(float *out, int64_t start, int64_t n, int64_t period,
                          int64_t phase_samples, float amplitude);
+/* K PeriodicTriggers in one launch (voice_bank.py): row v of `out` (n float32, out_stride elements apart, >= n) holds what
+ * pgx_periodic_trigger(start, n, periods[v], phase_samples[v], amplitudes[v]) writes, bit for bit -- the same integer
+ * test, the same rule for negative frames.  periods / phase_samples / amplitudes: device [batch] each, every period > 0 (a
+ * row whose period is not stays silent).  n <= 0 or batch <= 0: PGX_OK, nothing launched; batch > 65535, a stride below n
+ * (batch > 1), a null pointer: PGX_ERR_INVALID. */
+int pgx_periodic_trigger_bank(float *out, int64_t out_stride, int batch, int64_t start, int64_t n,
+                              const int64_t *periods, const int64_t *phase_samples, const float *amplitudes);
 /* PeriodicGate with PE-driven parameters: FunctionGenPE's stateful rectangle path (function_gen_pe.py:169-186).
  * A stream pointer overrides its scalar; state = { carried phase in cycles } (the host zeroes it when a
  * render is not contiguous with the previous one, function_gen_pe.py:170-171). */

@@ -389,6 +389,26 @@ __global__ void __launch_bounds__(kBlock) k_periodic_trigger(float *out, int64_t
     }
 }
 
+// K trigger rows in one launch (voice_bank.py): row blockIdx.y under its period, phase and amplitude, the same integer test.
+__global__ void __launch_bounds__(kBlock) k_periodic_trigger_bank(float *out, int64_t out_stride, int64_t start,
+                                                                  int64_t n, const int64_t *periods,
+                                                                  const int64_t *phase_samples, const float *amplitudes) {
+    const int64_t period = periods[blockIdx.y], phase = phase_samples[blockIdx.y];
+    const float amplitude = amplitudes[blockIdx.y];
+    float *o = out + (int64_t)blockIdx.y * out_stride;
+    const bool aligned = is_aligned16(o);
+    int64_t stride = (int64_t)gridDim.x * kBlock * kVec;
+    for (int64_t e = ((int64_t)blockIdx.x * kBlock + threadIdx.x) * kVec; e < n; e += stride) {
+        float v[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            int64_t a = start + e + j + phase;
+            v[j] = (period > 0 && a % period == 0) ? amplitude : 0.0f;     // (a period <= 0: a silent row)
+        }
+        store4(o, e, n, aligned, v);
+    }
+}
+
 // ------------------------------------------------------------------------------ SuperSaw voice sum
 // super_saw_pe.py:304-316: float64 accumulate of the float32 voices in voice order, * amp,
 // -> float32, tiled over channels.
@@ -642,6 +662,20 @@ int pgx_periodic_trigger(float *out, int64_t start, int64_t n, int64_t period, i
     hipLaunchKernelGGL(k_periodic_trigger, dim3(pgx::grid_for(pgx::ceil_div(n, kVec), kBlock)), dim3(kBlock), 0,
                        pgx::stream(), out, start, n, period, phase_samples, amplitude, is_aligned16(out));
     PGX_LAUNCH_CHECK("k_periodic_trigger");
+    return PGX_OK;
+}
+
+int pgx_periodic_trigger_bank(float *out, int64_t out_stride, int batch, int64_t start, int64_t n,
+                              const int64_t *periods, const int64_t *phase_samples, const float *amplitudes) {
+    PGX_REQUIRE_INIT();
+    if (n <= 0 || batch <= 0) return PGX_OK;
+    PGX_CHECK_ARG(out && periods && phase_samples && amplitudes, "pgx_periodic_trigger_bank: null pointer");
+    PGX_CHECK_ARG(batch == 1 || out_stride >= n, "pgx_periodic_trigger_bank: out_stride too small");
+    PGX_CHECK_ARG(batch <= 65535, "pgx_periodic_trigger_bank: batch too large");
+    dim3 grid(pgx::grid_for(pgx::ceil_div(n, kVec), kBlock), batch);
+    hipLaunchKernelGGL(k_periodic_trigger_bank, grid, dim3(kBlock), 0, pgx::stream(), out, out_stride, start, n, periods,
+                       phase_samples, amplitudes);
+    PGX_LAUNCH_CHECK("k_periodic_trigger_bank");
     return PGX_OK;
 }
 

@@ -3888,6 +3888,126 @@ k_svf(float *out, const float *in, int64_t n, int channels, double sr, const pgx
     }
 }
 
+// Bank of SVFilterPEs (pgx_svf_bank, voice_bank.py): k_svf with the voice in blockIdx.z.  What differs is where a
+// workgroup's data lies -- row v of in / out / freq / qs, params[v], gains[v], coef + 9 v, state[v][channel], voice v's
+// slice of the workspace (ws_doubles doubles each, laid out as pgx_svf lays out its one: snapshot[channel] in the first
+// 4 * channels doubles, then agg[channel][seg]); from `p` on the body is k_svf's, operation for operation, so a (voice,
+// channel, segment) workgroup writes the bits the single kernel writes for that voice.  p.mode, a_lin and `varying` are
+// uniform over the workgroup, as there.
+template <int MODE>
+__global__ void __launch_bounds__(kBlock)
+k_svf_bank(float *out, int64_t out_stride, const float *in, int64_t in_stride, int64_t n, int channels, double sr,
+           const pgx_biquad_var_params *params, const double *gains, const float *freq, int64_t freq_stride,
+           const float *qs, int64_t q_stride, const double *coef, double *state, double *workspace, int64_t ws_doubles,
+           int seg_tiles, int nseg) {
+    __shared__ BvShared sh;
+    const int tid = threadIdx.x;
+    const int seg = blockIdx.x, ch = blockIdx.y;
+    const int64_t v = blockIdx.z;
+    out += v * out_stride;
+    in += v * in_stride;
+    if (freq) freq += v * freq_stride;
+    if (qs) qs += v * q_stride;
+    if (coef) coef += v * 9;
+    const pgx_biquad_var_params p = params[v];
+    const double a_lin = gains[v];
+    double *snapshot = workspace ? workspace + v * ws_doubles : nullptr;
+    double *agg = snapshot ? snapshot + (int64_t)channels * 4 : nullptr;
+    double *st = state + (v * channels + ch) * 2;
+    const double *init = (MODE == 1) ? snapshot + ch * 2 : st;
+    double *ag = agg + ((int64_t)ch * nseg) * 6;
+    V2 carry{init[0], init[1]};
+    if (MODE == 1) carry = scan2_fold(ag, seg, carry);
+    if (MODE == 0 && seg == 0 && tid < 2) snapshot[ch * 2 + tid] = st[tid];
+    M2 acc_m = m_identity();
+    V2 acc_v{0.0, 0.0};
+    V2 final_s{0.0, 0.0};
+    bool have_final = false;
+    const bool varying = (freq != nullptr) || (qs != nullptr);
+    SvCoef cconst;
+    if (coef) {                                          // host-evaluated constant coefficients
+        cconst = SvCoef{coef[0], coef[1], coef[2], coef[3], coef[4], coef[5], coef[6], coef[7], coef[8]};
+    } else {
+        cconst = svf_coef(p.mode, p.freq, p.q, a_lin, sr);
+    }
+
+    const int64_t tile0 = (int64_t)seg * seg_tiles;
+    for (int t = 0; t < seg_tiles; ++t) {
+        const int64_t base = (tile0 + t) * kSvTile;
+        if (base >= n) break;
+        const int64_t f0 = base + (int64_t)tid * kSvT;
+        SvCoef cf[kSvT];
+        double xs[kSvT];
+        M2 cm = m_identity();
+        V2 cv{0.0, 0.0};
+        float x_in[kSvT], f_in[kSvT], q_in[kSvT];
+#pragma unroll
+        for (int j = 0; j < kSvT; ++j) {
+            const int64_t at = (f0 + j < n) ? f0 + j : n - 1;
+            x_in[j] = in[at * channels + ch];
+        }
+        if (varying && freq) {
+#pragma unroll
+            for (int j = 0; j < kSvT; ++j) f_in[j] = freq[(f0 + j < n) ? f0 + j : n - 1];
+        }
+        if (varying && qs) {
+#pragma unroll
+            for (int j = 0; j < kSvT; ++j) q_in[j] = qs[(f0 + j < n) ? f0 + j : n - 1];
+        }
+#pragma unroll
+        for (int j = 0; j < kSvT; ++j) {
+            const bool live = (f0 + j < n);
+            xs[j] = live ? (double)x_in[j] : 0.0;
+            if (varying) {
+                double f = p.freq, q = p.q;
+                if (freq) f = live ? (double)f_in[j] : 1000.0;
+                if (qs) q = live ? (double)q_in[j] : 1.0;
+                cf[j] = svf_coef(p.mode, f, q, a_lin, sr);
+            } else {
+                cf[j] = cconst;
+            }
+            if (live) {                                      // compose s' = A s + B x
+                const M2 A{cf[j].a00, cf[j].a01, cf[j].a10, cf[j].a11};
+                const V2 bx{cf[j].b0 * xs[j], cf[j].b1 * xs[j]};
+                cv = vadd(mv(A, cv), bx);
+                cm = mm(A, cm);
+            }
+        }
+        V2 s = scan2_tile<MODE>(sh, cm, cv, carry, acc_m, acc_v);
+        if (MODE == 0) continue;
+
+        float yf[kSvT];
+#pragma unroll
+        for (int j = 0; j < kSvT; ++j) {
+            const double xn = xs[j];
+            const double y = cf[j].c0 * xn + cf[j].c1 * s.x + cf[j].c2 * s.y;
+            yf[j] = (float)y;
+            if (f0 + j < n) {
+                const double n0 = cf[j].b0 * xn + cf[j].a00 * s.x + cf[j].a01 * s.y;
+                const double n1 = cf[j].b1 * xn + cf[j].a10 * s.x + cf[j].a11 * s.y;
+                s.x = n0;
+                s.y = n1;
+            }
+            if (f0 + j == n - 1) {
+                final_s = s;
+                have_final = true;
+            }
+        }
+        store_frames<kSvT>(out, f0, n, channels, ch, yf);
+    }
+    if (MODE == 0) {
+        if (tid == 0) {
+            double *a = ag + (int64_t)seg * 6;
+            a[0] = acc_m.a; a[1] = acc_m.b; a[2] = acc_m.c; a[3] = acc_m.d; a[4] = acc_v.x; a[5] = acc_v.y;
+        }
+        return;
+    }
+    if (have_final) {
+        st[0] = final_s.x;
+        st[1] = final_s.y;
+    }
+}
+
 // ================================================================================================
 // EnvelopePE (envelope_pe.py:128-271)
 // ================================================================================================
@@ -5268,6 +5388,41 @@ int pgx_svf(float *out, const float *in, int64_t n, int channels, double sample_
     hipLaunchKernelGGL(k_svf<1>, dim3(p.nseg, channels), dim3(kBlock), 0, pgx::stream(), out, in, n, channels,
                        sample_rate, params, freq, q, gain_a, coef, state, snap, agg, p.seg_tiles, p.nseg);
     PGX_LAUNCH_CHECK("k_svf<apply>");
+    return PGX_OK;
+}
+
+// The same plan per voice, the voice in grid.z (<= 65535); voice v's snapshot and maps lie at v times the single
+// entry's workspace size.
+int pgx_svf_bank(float *out, int64_t out_stride, const float *in, int64_t in_stride, int batch, int64_t n, int channels,
+                 double sample_rate, const pgx_biquad_var_params *params, const double *gains, const float *freq,
+                 int64_t freq_stride, const float *q, int64_t q_stride, const double *coef, double *state,
+                 void *workspace) {
+    PGX_REQUIRE_INIT();
+    if (n <= 0 || batch <= 0) return PGX_OK;
+    PGX_CHECK_ARG(out && in && params && gains && state && channels >= 1 && sample_rate > 0 && batch <= 65535,
+                  "pgx_svf_bank: bad argument");
+    PGX_CHECK_ARG(out_stride >= n * channels && in_stride >= n * channels && (!freq || freq_stride >= n) &&
+                      (!q || q_stride >= n),
+                  "pgx_svf_bank: a stride below its row");
+    PGX_CHECK_ARG(!(coef && (freq || q)), "pgx_svf_bank: constant coefficients exclude control streams");
+    const Scan2Plan p = scan2_plan(n, kSvTile);
+    double *ws = (double *)workspace;
+    const int64_t ws_doubles = (int64_t)channels * (4 + (int64_t)p.nseg * 6);      // pgx_scan2_workspace_bytes / 8
+    if (p.nseg <= 1 || workspace == nullptr) {
+        hipLaunchKernelGGL(k_svf_bank<2>, dim3(1, channels, batch), dim3(kBlock), 0, pgx::stream(), out, out_stride,
+                           in, in_stride, n, channels, sample_rate, params, gains, freq, freq_stride, q, q_stride, coef,
+                           state, (double *)nullptr, (int64_t)0, (int)pgx::ceil_div(n, kSvTile), 1);
+        PGX_LAUNCH_CHECK("k_svf_bank");
+        return PGX_OK;
+    }
+    hipLaunchKernelGGL(k_svf_bank<0>, dim3(p.nseg, channels, batch), dim3(kBlock), 0, pgx::stream(), out, out_stride, in,
+                       in_stride, n, channels, sample_rate, params, gains, freq, freq_stride, q, q_stride, coef, state,
+                       ws, ws_doubles, p.seg_tiles, p.nseg);
+    PGX_LAUNCH_CHECK("k_svf_bank<reduce>");
+    hipLaunchKernelGGL(k_svf_bank<1>, dim3(p.nseg, channels, batch), dim3(kBlock), 0, pgx::stream(), out, out_stride, in,
+                       in_stride, n, channels, sample_rate, params, gains, freq, freq_stride, q, q_stride, coef, state,
+                       ws, ws_doubles, p.seg_tiles, p.nseg);
+    PGX_LAUNCH_CHECK("k_svf_bank<apply>");
     return PGX_OK;
 }
 

@@ -14,8 +14,17 @@ bank produces the same samples as rendering the voices one by one.
 Supported nodes: SinePE (scalar), BlitSawPE (scalar), SuperSawPE (scalar), AnalogOscPE (scalar parameters, or
 single-channel PEs of batchable classes), BiquadPE (constant coefficients, or cutoff and / or Q driven by single-channel
 PEs of batchable classes), LadderPE (scalar controls), CombPE (scalar controls), GainPE (constant or PE gain), TransformPE
-(a chain lowered to pgx_transform), AdsrGatedPE, PeriodicGate.
+(a chain lowered to pgx_transform), AdsrGatedPE, PeriodicGate, SVFilterPE (scalar frequency and Q), AdsrTriggeredPE,
+PeriodicTrigger.
 Anything else -> `try_build_bank` returns None and MixPE falls back to per-input rendering.
+
+Percussive voices: a constant SVFilterPE is a level of its own (pgx_svf_bank, _SvfNode: pgx_svf's plan with the voice in
+the grid, the host's nine constants per voice; an SVFilterPE with a PE parameter stays per voice), and
+AdsrTriggeredPE(PeriodicTrigger) -- as a gain or under a TransformPE as a cutoff -- is two: K trigger rows in one launch
+(pgx_periodic_trigger_bank, _TriggerNode), then pgx_adsr_triggered with batch = K (_AdsrTriggeredNode, a plain node: the
+gated envelope's walk ahead of the stream is not for it; the on-chip mix takes its rows as any gain rows).  Banked from
+SVF_MIN_VOICES / ADSR_TRIGGERED_MIN_VOICES voices on, the walk from SVF_WALK_MIN_ROWS rows on (all three measured:
+tools/percussive_bank_probe.py).
 
 Swept-filter voices (pgx_biquad_varying_bank, _BiquadVarNode): a BiquadPE whose cutoff or Q is a PE -- an oscillator into a
 low-pass that follows an envelope or an LFO -- is a kind of its own, key ("biquad_var", freq_is_pe, q_is_pe, source, ...);
@@ -47,7 +56,7 @@ import numpy as np
 from . import device as _dev
 from ._kernels import DeviceBuffer, blitsaw_workspace, check, lib, ptr
 from . import transforms as _tf
-from .adsr_pe import AdsrGatedPE
+from .adsr_pe import AdsrGatedPE, AdsrTriggeredPE
 from .analog_osc_pe import AnalogOscPE
 from .biquad_pe import _MODE_INDEX, BiquadPE, rbj_coefficients, settle_frames, settle_frames_fine
 from .blit_saw_pe import BlitSawPE, wide_oscillators_ok
@@ -56,10 +65,12 @@ from .extent import Extent
 from .gain_pe import GainPE
 from .ladder_pe import LadderPE
 from .periodic_gate import PeriodicGate
+from .periodic_trigger import PeriodicTrigger
 from .processing_element import ProcessingElement
 from .sine_pe import SinePE
 from .snippet import Snippet
 from .super_saw_pe import SuperSawPE
+from .svfilter_pe import _SVF_MODE_INDEX, SVFilterPE, svf_coefficients
 from .transform_pe import TransformPE
 
 MIN_VOICES = 4
@@ -81,6 +92,23 @@ BIQUAD_VAR_WALK_MIN_ROWS = 512   # rows (voices x channels) from which _BiquadVa
                               # 120 / 141 and 112 / 132; 48 000 frames: 16 rows 231 / 91, 64: 271 / 179, 256: 344 / 435 and 308 / 392,
                               # 512: 521 / 807 and 470 / 727.  The smallest row count measured from which the walk is not slower in
                               # any row, and in no row of a larger count (256 loses one of its four: short streams of 4 096 frames)
+SVF_MIN_VOICES = 256          # ... and for voices that hold an SVFilterPE (_SvfNode): tools/percussive_bank_probe.py, SVFilterPE(BlitSawPE),
+                              # us per block bank / per voice over streams of 2 040 (248) blocks, look-ahead on -- 512-frame blocks:
+                              # 4 voices 17 / 1, 16: 21 / 4, 64: 20 / 14, 256: 21 / 59; 4 096: 20 / 1, 21 / 5, 26 / 19, 37 / 78; 48 000:
+                              # 21 / 9, 34 / 34, 91 / 138, 306 / 548 (profiles/percussive_bank_probe.md; the spread of three passes is
+                              # below 1 us in these rows).  Two PEs per voice in windows of up to 256 blocks cost the per-voice path
+                              # 0.25 us per voice and block; the bank pays its ~20 us every block.  The smallest K measured from which
+                              # the bank wins every row (64 loses at 512 and at 4 096 frames; between 64 and 256: not measured)
+SVF_WALK_MIN_ROWS = 256       # rows (voices x channels) from which _SvfNode passes no workspace: one workgroup per row walks the block in
+                              # one launch instead of the segmented plan's two.  The same probe, us per block walk / segmented -- 4 096
+                              # frames: 4 rows 18 / 20, 64: 21 / 26, 256: 25 / 37; 48 000 frames: 4 rows 109 / 21, 64: 123 / 91, 256: 150 /
+                              # 306 (blocks of up to two tiles are walked either way).  The smallest row count measured from which the
+                              # walk is not slower in any row
+ADSR_TRIGGERED_MIN_VOICES = 64   # ... and for voices that hold an AdsrTriggeredPE (_AdsrTriggeredNode): the same probe, GainPE(BiquadPE(
+                              # BlitSawPE), gain=AdsrTriggeredPE(PeriodicTrigger)), us per block bank / per voice -- 512-frame blocks: 4
+                              # voices 54 / 3, 16: 59 / 13, 32: 59 / 27, 64: 51 / 57, 256: 58 / 292; 4 096: 57 / 18, 8 voices 59 / 37, 16
+                              # (the on-chip mix from here on): 11 / 76, 64: 13 / 332, 256: 21 / 1 790; 48 000: 97 / 209, 16: 66 / 854,
+                              # 256: 195 / 20 490.  The smallest K measured from which the bank wins every row (32 loses at 512 frames)
 BANK_WINDOWS = True           # a small bank streamed in equal blocks: 2, 4, 8 blocks per render, handed out as rows (VoiceBank)
 BANK_WINDOWS_ANY_ROOT = os.environ.get("PGX_BANK_WINDOWS_ANY_ROOT", "0") == "1"     # experiments (C5: measured slower)
 BANK_WINDOW_FIRST = 2
@@ -837,6 +865,58 @@ class _BiquadVarNode(_Node):
         return out
 
 
+class _SvfNode(_Node):
+    """Bank of SVFilterPEs with scalar frequency and Q: pgx_svf_bank, the PE's kernel with the voice in the grid.  Per voice:
+    `params` and `gains` as SVFilterPE._render fills them (mode and gain_db are data, not part of the key) and `coef`, the
+    nine numbers of svfilter_pe.svf_coefficients the PE uploads -- so each voice's samples and {s0, s1} are the PE's, bit for
+    bit, while the node passes the workspace (the PE's segmented plan)."""
+
+    _STATE = ("state",)
+
+    def __init__(self, pes, children):
+        super().__init__(pes, children)
+        rec = np.zeros(self.k, dtype=_dev.BIQUAD_VAR_PARAMS)
+        gains = np.zeros(self.k, dtype=np.float64)
+        coef = np.zeros((self.k, 9), dtype=np.float64)
+        for i, pe in enumerate(pes):
+            rec[i]["freq"] = float(pe._frequency)
+            rec[i]["q"] = float(pe._q)
+            rec[i]["gain_db"] = float(pe._gain_db)
+            rec[i]["mode"] = _SVF_MODE_INDEX[pe._mode]
+            gains[i] = 10.0 ** (pe._gain_db / 40.0)
+            coef[i] = svf_coefficients(pe._mode, pe._frequency, pe._q, pe._gain_db, self.sr)
+        self.params = _dev.upload_structs(rec)
+        self.gains = DeviceBuffer.from_host(gains)
+        self.coef = DeviceBuffer.from_host(coef)
+        self.state = None
+        self.ws = None
+
+    def reset(self):
+        super().reset()
+        if self.state is not None:
+            self.state.zero_()
+
+    def channels(self):
+        return self.children["source"].channels()
+
+    def render(self, start, n):
+        L = lib()
+        x = self.children["source"].render(start, n)
+        ch = x.shape[2]
+        if self.state is None:
+            self.state = DeviceBuffer((self.k, ch, 2), np.float64, zero=True)
+        # (as _BiquadVarNode: enough rows to give every CU a workgroup -> each row walked by one workgroup in one launch)
+        walk = self.k * ch >= SVF_WALK_MIN_ROWS
+        need = 0 if walk else self.k * L.pgx_scan2_workspace_bytes(n, ch)
+        if need and (self.ws is None or self.ws.nbytes < need):
+            self.ws = DeviceBuffer((need,), np.uint8)
+        out = DeviceBuffer((self.k, n, ch), np.float32)
+        check(L.pgx_svf_bank(out.ptr, n * ch, x.ptr, getattr(x, "stride", n * ch), self.k, n, ch, self.sr,
+                             self.params.ptr, self.gains.ptr, None, 0, None, 0, self.coef.ptr, self.state.ptr,
+                             ptr(self.ws) if need else None), "pgx_svf_bank")
+        return out
+
+
 class _LadderNode(_Windowed, _Node):
     """Bank of LadderPEs.  The ladder kernel is latency-bound (two waves per CU, most of the chip idle) and its
     input, a bank of scalar oscillators, is a pure function of time plus a few carried numbers -- so while block k
@@ -1028,6 +1108,57 @@ class _GateNode(_Node):
     def render(self, start, n):
         out = DeviceBuffer((self.k, n, 1), np.float32)
         check(lib().pgx_periodic_gate(out.ptr, n, self.k, start, n, self.params.ptr), "pgx_periodic_gate")
+        return out
+
+
+class _TriggerNode(_Node):
+    """Bank of PeriodicTriggers: K rows of impulses in one launch (pgx_periodic_trigger_bank), integer arithmetic."""
+
+    def __init__(self, pes):
+        super().__init__(pes, {})
+        self.periods = DeviceBuffer.from_host(np.array([pe._period for pe in pes], dtype=np.int64))
+        self.phases = DeviceBuffer.from_host(np.array([pe._phase_samples for pe in pes], dtype=np.int64))
+        self.amplitudes = DeviceBuffer.from_host(np.array([float(pe._amp) for pe in pes], dtype=np.float32))
+
+    def channels(self):
+        return 1
+
+    def render(self, start, n):
+        out = DeviceBuffer((self.k, n, 1), np.float32)
+        check(lib().pgx_periodic_trigger_bank(out.ptr, n, self.k, start, n, self.periods.ptr, self.phases.ptr,
+                                              self.amplitudes.ptr), "pgx_periodic_trigger_bank")
+        return out
+
+
+class _AdsrTriggeredNode(_Node):
+    """Bank of AdsrTriggeredPEs: one pgx_adsr_triggered call with batch = K over the trigger rows, {state, env,
+    sustain_ends_at} carried per voice.  A plain node: nothing of it runs ahead of the stream (_AdsrGatedNode's side-stream
+    walk is for the fused PeriodicGate)."""
+
+    _STATE = ("state",)
+
+    def __init__(self, pes, children):
+        super().__init__(pes, children)
+        self.params = _dev.upload_structs(_param_records(_dev.ADSR_PARAMS, pes, lambda pe: pe._adsr_params()))
+        self.state = DeviceBuffer((self.k, 3), np.float64, zero=True)
+        self.ws = None
+
+    def reset(self):
+        super().reset()
+        self.state.zero_()
+
+    def channels(self):
+        return 1
+
+    def render(self, start, n):
+        L = lib()
+        trig = self.children["trigger"].render(start, n)
+        need = L.pgx_adsr_workspace_bytes(self.k, n)
+        if self.ws is None or self.ws.nbytes < need:
+            self.ws = DeviceBuffer((need,), np.uint8)
+        out = DeviceBuffer((self.k, n, 1), np.float32)
+        check(L.pgx_adsr_triggered(out.ptr, n, trig.ptr, getattr(trig, "stride", n), self.k, start, n, self.params.ptr,
+                                   self.state.ptr, self.ws.ptr), "pgx_adsr_triggered")
         return out
 
 
@@ -1297,11 +1428,17 @@ _KINDS = (
           (_SOURCE, ("frequency", "_frequency", lambda pe: pe._freq_is_pe), ("q", "_q", lambda pe: pe._q_is_pe)),
           lambda pes, children: (_BiquadVarNode if _biquad_swept(pes[0]) else _BiquadNode)(pes, children),
           lambda pe: BIQUAD_VAR_MIN_VOICES if _biquad_swept(pe) else MIN_VOICES),
+    # (scalar frequency and Q only -- a PE-driven SVFilterPE stays per voice; mode, gain_db and the scalars are per-voice data)
+    _Kind(SVFilterPE, "svf", lambda pe: not (pe._freq_is_pe or pe._q_is_pe), None, (_SOURCE,), _SvfNode,
+          lambda pe: SVF_MIN_VOICES),
     _Kind(LadderPE, "ladder", lambda pe: not (pe._freq_is_pe or pe._res_is_pe or pe._drive_is_pe), None, (_SOURCE,),
           _LadderNode),
     _Kind(CombPE, "comb", lambda pe: not (pe._freq_is_pe or pe._fb_is_pe), None, (_SOURCE,), _CombNode),
     _Kind(PeriodicGate, "gate", lambda pe: pe.is_pure(), None, (), _GateNode),       # PE-driven gates carry a phase: not batched
     _Kind(AdsrGatedPE, "adsr_gated", _ALWAYS, None, (("gate", "_gate", _ALWAYS),), _AdsrGatedNode),
+    _Kind(PeriodicTrigger, "trigger", _ALWAYS, None, (), _TriggerNode),
+    _Kind(AdsrTriggeredPE, "adsr_trig", _ALWAYS, None, (("trigger", "_trigger", _ALWAYS),), _AdsrTriggeredNode,
+          lambda pe: ADSR_TRIGGERED_MIN_VOICES),
     _Kind(GainPE, lambda pe: "gain_pe" if pe._gain_is_pe else "gain", _ALWAYS, None,
           (_SOURCE, ("gain", "_gain", lambda pe: pe._gain_is_pe)), _GainNode),
 )
