@@ -736,6 +736,17 @@ int pgx_slew(float *out, const float *in, int in_channels, int64_t n, int mode, 
  * copies of the column.  duty is clipped to [0, 1] here (:184).  Bit-exact. */
 int pgx_function_gen_pure(float *out, int64_t start, int64_t n, int channels, int sawtooth, double dt, double phase,
                           double duty);
+/* `batch` pure FunctionGenPEs of one waveform and channel count in one launch (voice_bank.py; function_gen_pe.py:166-168,
+ * :180-193 per instance): instance v writes n frames of `channels` interleaved copies at out + v * out_stride, the
+ * samples of pgx_function_gen_pure(start, n, channels, sawtooth, params[v].dt, params[v].phase, params[v].duty) -- the
+ * same per-sample device function, the instance in the grid.  Bit-exact.  dt = freq / sample_rate as the PE forms it.
+ * n <= 0 or batch <= 0: nothing is launched.  A null pointer, channels < 1, out_stride < n * channels (batch > 1),
+ * batch > 65535: PGX_ERR_INVALID.
+ * pgx_function_gen_params is { double dt; double phase; double duty; } -- pgx_gate_params' record under the name of
+ * this PE (the gate is this generator's rectangle, periodic_gate.py:63-67); duty is clipped in the kernel here. */
+typedef pgx_gate_params pgx_function_gen_params;
+int pgx_function_gen_bank(float *out, int64_t out_stride, int batch, int64_t start, int64_t n, int channels,
+                          int sawtooth, const pgx_function_gen_params *params);
 /* FunctionGenPE._render with any PE parameter (function_gen_pe.py:169-177): base = mod(state[0] + [0,
  * cumsum(f / sr)[:-1]], 1), then state[0] = mod(state[0] + sum(f / sr), 1); the float64 prefix sum runs over
  * workgroup segments.  A stream pointer (mono, n floats) overrides its scalar; the host zeroes the state when a

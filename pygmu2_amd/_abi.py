@@ -1,8 +1,9 @@
 """
 Strict reader of include/pygmu_hip.h, the one definition of the library's C ABI: every prototype as ctypes classes,
 every parameter struct as a packed numpy dtype, every PGX_* constant.  Inside the header's extern "C" block a
-statement is a #define, the status enum, a typedef struct or a prototype; anything else, and any type name not listed
-here, raises AbiError with its line -- a declaration is never skipped.
+statement is a #define, the status enum, a typedef struct, a second name for an earlier struct (`typedef pgx_a pgx_b;`:
+the same type to the compiler, the same dtype here, no table entry of its own) or a prototype; anything else, and any
+type name not listed here, raises AbiError with its line -- a declaration is never skipped.
 """
 
 from __future__ import annotations
@@ -28,6 +29,7 @@ _SPACE = re.compile(r"\s*")
 _DEFINE = re.compile(r"#define[ \t]+(PGX_\w+)[ \t]+(.*)")
 _ENUM = re.compile(r"typedef\s+enum\s*\{([^{}]*)\}\s*pgx_\w+\s*;")
 _STRUCT = re.compile(r"typedef\s+struct\s*\{([^{}]*)\}\s*(pgx_\w+)\s*;")
+_ALIAS = re.compile(r"typedef\s+(pgx_\w+)\s+(pgx_\w+)\s*;")
 _PROTOTYPE = re.compile(r"([^;{}#()]+)\(([^;{}#()]*)\)\s*;")
 # [PGX_HOST] [const] type [* [const]]... name [[N]]
 _DECLARATION = re.compile(r"(PGX_HOST\s+)?(?:const\s+)?(\w+)\s*((?:\*\s*(?:const\s*)?)*)\b(\w+)\s*(?:\[(\d*)\])?")
@@ -38,9 +40,11 @@ class Abi:
     def __init__(self):
         self.functions = {}        # name -> (restype, [argtypes]), header order
         self.structs = {}          # pgx_name -> np.dtype
+        self.aliases = {}          # pgx_name -> the pgx_name of the struct it is another name for
         self.constants = {}        # PGX_NAME -> int | float
 
     def struct(self, name: str) -> np.dtype:
+        name = self.aliases.get(name, name)
         if name not in self.structs:
             raise AbiError(f"pygmu_hip.h declares no struct {name}")
         return self.structs[name]
@@ -137,10 +141,16 @@ def parse(text: str) -> Abi:
                 abi.constants[name.strip()] = _evaluate(value, abi.constants, line)
         elif m := _STRUCT.match(text, pos, end):
             abi.structs[m.group(2)] = _dtype(m.group(1), abi.structs, line)
+        elif m := _ALIAS.match(text, pos, end):
+            if m.group(1) not in abi.structs or m.group(2) in abi.structs or m.group(2) in abi.aliases:
+                raise AbiError(f"pygmu_hip.h:{line}: {m.group(2)!r} must be a new name for an earlier struct, "
+                               f"which {m.group(1)!r} is not")
+            abi.aliases[m.group(2)] = m.group(1)
         elif m := _PROTOTYPE.match(text, pos, end):
-            restype, name = _ctype(m.group(1), abi.structs, line, returned=True)
+            known = abi.structs.keys() | abi.aliases.keys()
+            restype, name = _ctype(m.group(1), known, line, returned=True)
             params = [] if m.group(2).strip() == "void" else m.group(2).split(",")
-            abi.functions[name] = (restype, [_ctype(p, abi.structs, line)[0] for p in params])
+            abi.functions[name] = (restype, [_ctype(p, known, line)[0] for p in params])
         else:
             raise AbiError(f"pygmu_hip.h:{line}: not a #define, enum, struct or prototype: "
                            f"{text[pos:end].splitlines()[0]!r}")

@@ -1,5 +1,5 @@
 // pgx_control.hip -- the control-signal PEs: SampleHoldPE / TrackHoldPE (pgx_hold), SlewLimiterPE (pgx_slew) and
-// FunctionGenPE (pgx_function_gen_pure / pgx_function_gen_stateful).
+// FunctionGenPE (pgx_function_gen_pure / pgx_function_gen_bank / pgx_function_gen_stateful).
 //
 // All three are sequential per-sample loops in the reference.  Here:
 //   * a hold is a max-scan over indices ("the last frame whose control sample passed") followed by a gather --
@@ -479,14 +479,62 @@ __device__ __forceinline__ double fg_wave(double p, double duty, int saw) {
     return saw ? fg_saw(p, duty) : (p < duty ? 1.0 : -1.0);
 }
 
-// all parameters scalar: phase = mod(mod(n * dt, 1) + ph, 1) (:166-180), `channels` copies of the column
+// all parameters scalar: phase = mod(mod(n * dt, 1) + ph, 1) (:166-180) -- the sample of frame `frame`, what
+// k_fg_pure and k_fg_bank both store
+__device__ __forceinline__ float fg_pure_sample(int64_t frame, double dt, double ph, double duty, int saw) {
+    const double base = pgx::pgx_mod1((double)frame * dt);
+    return (float)fg_wave(pgx::pgx_mod1(base + ph), duty, saw);
+}
+
+// ... `channels` copies of the column
 __global__ void __launch_bounds__(kBlock)
 k_fg_pure(float *out, int64_t start, int64_t n, int channels, double dt, double ph, double duty, int saw) {
     const int64_t stride = (int64_t)gridDim.x * kBlock;
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
-        const double base = pgx::pgx_mod1((double)(start + i) * dt);
-        const float y = (float)fg_wave(pgx::pgx_mod1(base + ph), duty, saw);
+        const float y = fg_pure_sample(start + i, dt, ph, duty, saw);
         for (int c = 0; c < channels; ++c) out[i * channels + c] = y;
+    }
+}
+
+// K of them in one launch (voice_bank.py): instance blockIdx.y under params[blockIdx.y], its row out_stride floats
+// after the one before.  A workgroup renders tiles of kFgBankTile = 1024 frames, kFgBankT per thread.  A mono row that
+// is 16-byte aligned: a thread owns 4 consecutive frames and stores one float4 (the layout of k_sine / k_periodic_gate;
+// the row's last, partial group as scalars).  Any other row: a thread owns frames tid, tid + 256, ... of the tile, so
+// that a wave's scalar stores are consecutive (k_fg_pure's layout), `channels` copies a frame.
+constexpr int kFgBankT = 4;
+constexpr int kFgBankTile = kBlock * kFgBankT;
+
+__global__ void __launch_bounds__(kBlock)
+k_fg_bank(float *out, int64_t out_stride, int64_t start, int64_t n, int channels, int saw,
+          const pgx_function_gen_params *params) {
+    const pgx_function_gen_params p = params[blockIdx.y];
+    float *o = out + (int64_t)blockIdx.y * out_stride;
+    const bool vec = channels == 1 && aligned16(o);
+    const int64_t stride = (int64_t)gridDim.x * kFgBankTile;
+    for (int64_t tile = (int64_t)blockIdx.x * kFgBankTile; tile < n; tile += stride) {
+        if (vec) {
+            const int64_t f0 = tile + (int64_t)threadIdx.x * kFgBankT;
+            if (f0 >= n) continue;
+            float y[kFgBankT];
+#pragma unroll
+            for (int j = 0; j < kFgBankT; ++j) y[j] = fg_pure_sample(start + f0 + j, p.dt, p.phase, p.duty, saw);
+            if (f0 + kFgBankT <= n) {
+                *reinterpret_cast<float4 *>(o + f0) = make_float4(y[0], y[1], y[2], y[3]);
+            } else {
+#pragma unroll
+                for (int j = 0; j < kFgBankT; ++j)
+                    if (f0 + j < n) o[f0 + j] = y[j];
+            }
+            continue;
+        }
+#pragma unroll
+        for (int j = 0; j < kFgBankT; ++j) {
+            const int64_t f = tile + (int64_t)j * kBlock + threadIdx.x;
+            if (f < n) {
+                const float y = fg_pure_sample(start + f, p.dt, p.phase, p.duty, saw);
+                for (int c = 0; c < channels; ++c) o[f * channels + c] = y;
+            }
+        }
     }
 }
 
@@ -655,6 +703,20 @@ int pgx_function_gen_pure(float *out, int64_t start, int64_t n, int channels, in
     hipLaunchKernelGGL(k_fg_pure, dim3(pgx::grid_for(n, kBlock)), dim3(kBlock), 0, pgx::stream(), out, start, n,
                        channels, dt, phase, duty, sawtooth ? 1 : 0);
     PGX_LAUNCH_CHECK("k_fg_pure");
+    return PGX_OK;
+}
+
+int pgx_function_gen_bank(float *out, int64_t out_stride, int batch, int64_t start, int64_t n, int channels,
+                          int sawtooth, const pgx_function_gen_params *params) {
+    PGX_REQUIRE_INIT();
+    if (n <= 0 || batch <= 0) return PGX_OK;
+    PGX_CHECK_ARG(out && params && channels >= 1, "pgx_function_gen_bank: bad argument");
+    PGX_CHECK_ARG(batch == 1 || out_stride >= n * channels, "pgx_function_gen_bank: out_stride too small");
+    PGX_CHECK_ARG(batch <= 65535, "pgx_function_gen_bank: batch too large");
+    dim3 grid(pgx::grid_for(pgx::ceil_div(n, kFgBankT), kBlock), batch);
+    hipLaunchKernelGGL(k_fg_bank, grid, dim3(kBlock), 0, pgx::stream(), out, out_stride, start, n, channels,
+                       sawtooth ? 1 : 0, params);
+    PGX_LAUNCH_CHECK("k_fg_bank");
     return PGX_OK;
 }
 

@@ -60,6 +60,7 @@ REVERSE_ECHO_STATE = _ABI.struct("pgx_reverse_echo_state")
 NOISE_PARAMS = _ABI.struct("pgx_noise_params")
 NOISE_STATE = _ABI.struct("pgx_noise_state")
 ADSR_PARAMS = _ABI.struct("pgx_adsr_params")
+FUNCTION_GEN_PARAMS = _ABI.struct("pgx_function_gen_params")
 
 # and its constants
 ERR_INVALID = _ABI.constant("PGX_ERR_INVALID")

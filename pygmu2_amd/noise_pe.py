@@ -11,6 +11,9 @@ brown level live in HBM.  Samples are the reference's to the bit in all three mo
 Like the reference, `start` is ignored: every render consumes the next `duration` draws wherever it is asked to be.  A
 seek does not rewind the stream; only on_start / reset_state() does (generator back to the seed, taps and level zero;
 seed=None draws fresh OS entropy, as default_rng(None) does).
+
+A MixPE of many NoisePEs of one mode renders them as a bank (voice_bank._NoiseNode: the same kernels with batch = K); the
+node then holds the voices' records, and advance() / reset_state() on a voice are passed on to it (`_bank_slot`).
 """
 
 from __future__ import annotations
@@ -51,6 +54,7 @@ class NoisePE(SourcePE):
         self._params: DeviceBuffer | None = None      # one pgx_noise_params; None until the first render after a start
         self._filter: DeviceBuffer | None = None      # one pgx_noise_state; None: all zero
         self._consumed = 0                            # draws taken since the generator was seeded
+        self._bank_slot = None                        # (weakref to the voice bank node that renders this PE, its voice)
 
     min_value = property(lambda self: self._min_value)
     max_value = property(lambda self: self._max_value)
@@ -73,6 +77,14 @@ class NoisePE(SourcePE):
         self._params = None             # the next render seeds the generator again
         self._filter = None
         self._consumed = 0
+        node = self._bank_node()
+        if node is not None:
+            node.reset_voice(self._bank_slot[1])
+
+    def _bank_node(self):
+        """The voice bank node that renders this PE (voice_bank._NoiseNode; this PE is its voice _bank_slot[1]), or None."""
+        slot = self._bank_slot
+        return slot[0]() if slot is not None else None
 
     _on_start = _reset_state
     _on_stop = _reset_state
@@ -83,8 +95,12 @@ class NoisePE(SourcePE):
         if draws < 0:
             raise ValueError("draws must be >= 0")
         self._consumed += int(draws)
+        node = self._bank_node()
+        if node is not None:                # a voice of a bank: its record there skips ahead
+            node.advance(self._bank_slot[1], int(draws))
 
-    def _seed_generator(self) -> None:
+    def _seed_record(self) -> np.ndarray:
+        """One pgx_noise_params for the seeded generator (seed=None: fresh OS entropy at every call)."""
         s = np.random.PCG64(self._seed).state["state"]
         state, inc = int(s["state"]), int(s["inc"])
         rec = np.zeros(1, dtype=_dev.NOISE_PARAMS)
@@ -94,7 +110,10 @@ class NoisePE(SourcePE):
         with np.errstate(over="ignore"):
             rec["span"] = np.float32(self._max_value - self._min_value)
             rec["min_value"] = np.float32(self._min_value)
-        self._params = _dev.upload_structs(rec)
+        return rec
+
+    def _seed_generator(self) -> None:
+        self._params = _dev.upload_structs(self._seed_record())
 
     def _render(self, start: int, duration: int) -> Snippet:
         if duration <= 0:

@@ -11,7 +11,8 @@ K voices in input order in float32 -- the same additions, in the same order, as 
 The batched kernels are the very same kernels the single PEs use (batch = 1 there), so a
 bank produces the same samples as rendering the voices one by one.
 
-Supported nodes: SinePE (scalar), BlitSawPE (scalar), SuperSawPE (scalar), AnalogOscPE (scalar parameters, or
+Supported nodes: SinePE (scalar), FunctionGenPE (scalar), NoisePE, BlitSawPE (scalar), SuperSawPE (scalar),
+AnalogOscPE (scalar parameters, or
 single-channel PEs of batchable classes), BiquadPE (constant coefficients, or cutoff and / or Q driven by single-channel
 PEs of batchable classes), LadderPE (scalar controls), CombPE (scalar controls), GainPE (constant or PE gain), TransformPE
 (a chain lowered to pgx_transform), AdsrGatedPE, PeriodicGate, SVFilterPE (scalar frequency and Q), AdsrTriggeredPE,
@@ -25,6 +26,14 @@ AdsrTriggeredPE(PeriodicTrigger) -- as a gain or under a TransformPE as a cutoff
 gated envelope's walk ahead of the stream is not for it; the on-chip mix takes its rows as any gain rows).  Banked from
 SVF_MIN_VOICES / ADSR_TRIGGERED_MIN_VOICES voices on, the walk from SVF_WALK_MIN_ROWS rows on (all three measured:
 tools/percussive_bank_probe.py).
+
+Noise voices (_NoiseNode): pgx_noise_white / _pink / _brown have taken a batch since they were written -- an instance per grid
+row or workgroup, params[i], state[i] -- so K NoisePEs of one mode are ONE call, and K pink or brown recurrences stepped side by
+side last as long as one.  Seed and range are per-voice data, the draws consumed are one host number (every voice takes n per
+render); NoisePE.advance / reset_state on one voice move that voice's record alone.  A hi-hat voice -- GainPE(SVFilterPE(NoisePE),
+gain=AdsrTriggeredPE(PeriodicTrigger)) -- is batched on every level.  Banked from NOISE_MIN_VOICES voices on (measured:
+tools/noise_bank_probe.py).  A pure FunctionGenPE (_FunctionGenNode: pgx_function_gen_bank, the PE's sample function with the
+voice in the grid, bit for bit) is a source or a modulator like SinePE; one with a PE parameter carries a phase and stays per voice.
 
 Swept-filter voices (pgx_biquad_varying_bank, _BiquadVarNode): a BiquadPE whose cutoff or Q is a PE -- an oscillator into a
 low-pass that follows an envelope or an LFO -- is a kind of its own, key ("biquad_var", freq_is_pe, q_is_pe, source, ...);
@@ -49,6 +58,7 @@ from __future__ import annotations
 import functools
 import math
 import os
+import weakref
 from typing import NamedTuple
 
 import numpy as np
@@ -62,8 +72,10 @@ from .biquad_pe import _MODE_INDEX, BiquadPE, rbj_coefficients, settle_frames, s
 from .blit_saw_pe import BlitSawPE, wide_oscillators_ok
 from .comb_pe import CombPE
 from .extent import Extent
+from .function_gen_pe import FunctionGenPE
 from .gain_pe import GainPE
 from .ladder_pe import LadderPE
+from .noise_pe import _MASK64, NoiseMode, NoisePE
 from .periodic_gate import PeriodicGate
 from .periodic_trigger import PeriodicTrigger
 from .processing_element import ProcessingElement
@@ -109,6 +121,15 @@ ADSR_TRIGGERED_MIN_VOICES = 64   # ... and for voices that hold an AdsrTriggered
                               # voices 54 / 3, 16: 59 / 13, 32: 59 / 27, 64: 51 / 57, 256: 58 / 292; 4 096: 57 / 18, 8 voices 59 / 37, 16
                               # (the on-chip mix from here on): 11 / 76, 64: 13 / 332, 256: 21 / 1 790; 48 000: 97 / 209, 16: 66 / 854,
                               # 256: 195 / 20 490.  The smallest K measured from which the bank wins every row (32 loses at 512 frames)
+NOISE_MIN_VOICES = 64         # ... and for voices that hold a NoisePE (_NoiseNode): tools/noise_bank_probe.py, MixPE of K NoisePE(seed=i), us
+                              # per block bank / per voice, look-ahead on, streams of 248 blocks of 1 024 frames and of 8 of 48 000
+                              # (profiles/noise_bank_probe.md; the spread of three passes is below 3 us in the rows that decide).  White,
+                              # the mode that decides -- 1 024 frames: 4 voices 12 / 2, 8: 11 / 3, 16: 12 / 5.5, 64: 11 / 20, 256: 13 / 78,
+                              # 512: 19 / 177; 48 000: 14 / 27, 18 / 58, 15 / 89, 24 / 330, 59 / 1 293, 104 / 2 580.  Pink and brown win
+                              # from 4 voices on (pink 1 024 frames: 25 / 70 ... 41 / 9 089; 48 000: 846 / 3 659 ... 1 041 / 472 907: K
+                              # recurrences side by side last as long as one), the hi-hat voice from 64 (16 voices, 1 024 frames: 61 / 50).
+                              # The smallest K measured at which the bank is not slower at either block length in ANY mode, nor at a
+                              # larger K (between 16 and 64: not measured).  One number for the three modes: a minimum per mode is open
 BANK_WINDOWS = True           # a small bank streamed in equal blocks: 2, 4, 8 blocks per render, handed out as rows (VoiceBank)
 BANK_WINDOWS_ANY_ROOT = os.environ.get("PGX_BANK_WINDOWS_ANY_ROOT", "0") == "1"     # experiments (C5: measured slower)
 BANK_WINDOW_FIRST = 2
@@ -364,6 +385,122 @@ class _SineNode(_Node):
         out = DeviceBuffer((self.k, n, self.ch), np.float32)
         check(lib().pgx_sine_render(out.ptr, n * self.ch, self.k, start, n, self.ch, self.sr,
                                     self.params.ptr), "pgx_sine_render")
+        return out
+
+
+class _FunctionGenNode(_Node):
+    """Bank of pure FunctionGenPEs of one waveform and channel count: pgx_function_gen_bank, pgx_function_gen_pure's
+    sample function with the voice in the grid.  Stateless, like _SineNode: dt, phase and duty are the PE's expressions."""
+
+    def __init__(self, pes):
+        super().__init__(pes, {})
+        rec = np.zeros(self.k, dtype=_dev.FUNCTION_GEN_PARAMS)
+        for i, pe in enumerate(pes):
+            rec[i] = (float(np.float64(pe._frequency) / self.sr), float(pe._phase_in), float(pe._duty_cycle))
+        self.params = _dev.upload_structs(rec)
+        self.saw = int(pes[0]._waveform == FunctionGenPE.WAVE_SAWTOOTH)
+        self.ch = pes[0]._channels
+
+    def channels(self):
+        return self.ch
+
+    def render(self, start, n):
+        out = DeviceBuffer((self.k, n, self.ch), np.float32)
+        check(lib().pgx_function_gen_bank(out.ptr, n * self.ch, self.k, start, n, self.ch, self.saw, self.params.ptr),
+              "pgx_function_gen_bank")
+        return out
+
+
+def _wrap_i64(value: int) -> int:
+    """`value` modulo 2^64 as the int64 of pgx_noise_params.consumed (the kernel adds it to `draws` as uint64)."""
+    value &= _MASK64
+    return value - (1 << 64) if value >> 63 else value
+
+
+class _NoiseNode(_Node):
+    """Bank of NoisePEs of one mode: the PE's kernel with batch = K (pgx_noise_white / _pink / _brown: an instance per
+    grid row / workgroup, params[i], state[i]) -- K pink or brown recurrences stepped side by side last as long as one.
+    `rec` / `params`: one record per voice, filled as NoisePE._seed_generator fills its one; `state`: the voices' taps
+    and levels (pink, brown); `draws`: what every voice has consumed since the seed -- all of them n per render, so one
+    number.  Like the PE, `start` is ignored and nothing depends on how the stream is cut.  NoisePE.advance(d) and
+    reset_state() on one voice reach `advance` and `reset_voice` (NoisePE._bank_slot): that voice's record alone moves,
+    by its `consumed` field -- draws + consumed, modulo 2^64, is where the voice stands."""
+
+    _STATE = ("state", "draws", "params")
+
+    def __init__(self, pes):
+        super().__init__(pes, {})
+        mode = pes[0]._mode
+        self.entry = {NoiseMode.WHITE: "pgx_noise_white", NoiseMode.PINK: "pgx_noise_pink",
+                      NoiseMode.BROWN: "pgx_noise_brown"}[mode]
+        self.state = None if mode is NoiseMode.WHITE else DeviceBuffer((self.k,), _dev.NOISE_STATE, zero=True)
+        self.bank = None             # weakref to the VoiceBank that renders this node (VoiceBank.__init__)
+        self._seed()
+        for i, pe in enumerate(pes):
+            pe._bank_slot = (weakref.ref(self), i)
+
+    def _seed(self) -> None:
+        """Every generator back to its seed (seed=None: fresh entropy, per voice, every time), no draw consumed."""
+        self.rec = np.concatenate([pe._seed_record() for pe in self.pes])
+        self.params = _dev.upload_structs(self.rec)
+        self.draws = 0
+        self.pending = set()         # voices whose own reset_state() waits for the next render (reset_voice)
+
+    def reset(self):
+        """NoisePE._reset_state and what the render after it does: reseed, taps and level zero."""
+        self._seed()
+        if self.state is not None:
+            self.state.zero_()
+
+    def _settle_bank(self) -> None:
+        """A window the bank has run ahead by holds samples of the streams as they were: the states go back to the last
+        block handed out before a voice's stream is moved."""
+        bank = self.bank() if self.bank is not None else None
+        if bank is not None:
+            bank._settle_window()
+
+    def reset_voice(self, voice: int) -> None:
+        """NoisePE.reset_state() (on_start, on_stop) on one voice: that voice alone starts over with the next render."""
+        self._settle_bank()
+        self.pending.add(voice)
+
+    def quiesce(self, keep=None) -> None:
+        """VoiceBank calls this on every node in front of the snapshot a new window goes back to: resets that wait are
+        applied first, so that the snapshot holds the records and taps the window is rendered from.  (Nothing waits while
+        a window is open: reset_voice and advance settle it before they touch anything.)"""
+        if self.pending:
+            self._apply_pending()
+
+    def _apply_pending(self) -> None:
+        if len(self.pending) == self.k:
+            return self.reset()
+        for i in sorted(self.pending):
+            self.rec[i] = self.pes[i]._seed_record()[0]
+            self.rec["consumed"][i] = _wrap_i64(-self.draws)               # consumed + draws = 0: the seed's first draw is next
+            if self.state is not None:
+                check(lib().pgx_memset(self.state.offset_ptr(i), 0, self.state.dtype.itemsize), "pgx_memset")
+        self.params = _dev.upload_structs(self.rec)
+        self.pending = set()
+
+    def advance(self, voice: int, draws: int) -> None:
+        """NoisePE.advance on one voice: its record alone skips `draws` draws, taps and level stay."""
+        self._settle_bank()
+        if self.pending:
+            self._apply_pending()
+        self.rec["consumed"][voice] = _wrap_i64(int(self.rec["consumed"][voice]) + int(draws))
+        self.params = _dev.upload_structs(self.rec)
+
+    def channels(self):
+        return 1
+
+    def render(self, start, n):
+        if self.pending:
+            self._apply_pending()
+        out = DeviceBuffer((self.k, n, 1), np.float32)
+        entry = getattr(lib(), self.entry)
+        args = (out.ptr, n, self.k, n, self.draws & _MASK64, self.params.ptr)
+        check(entry(*args) if self.state is None else entry(*args, self.state.ptr), self.entry)
+        self.draws += n
         return out
 
 
@@ -1411,6 +1548,11 @@ def _transform_codes(pe):
 
 _KINDS = (
     _Kind(SinePE, "sine", lambda pe: not pe._has_pe_inputs(), lambda pe: (pe._channels,), (), _SineNode),
+    # (a FunctionGenPE with a PE parameter carries a phase and restarts on a seek: not batched -- PeriodicGate's rule)
+    _Kind(FunctionGenPE, "function_gen", lambda pe: pe.is_pure(), lambda pe: (pe._waveform, pe._channels), (),
+          _FunctionGenNode),
+    # (one kernel per mode: part of the key; range and seed are per-voice data)
+    _Kind(NoisePE, "noise", _ALWAYS, lambda pe: (pe._mode.value,), (), _NoiseNode, lambda pe: NOISE_MIN_VOICES),
     _Kind(BlitSawPE, "blitsaw", lambda pe: not pe.inputs(), lambda pe: (pe._channels,), (), _BlitSawNode),
     _Kind(SuperSawPE, "supersaw", lambda pe: not pe.inputs(), lambda pe: (pe._channels, len(pe._oscillators)), (),
           _SuperSawNode),
@@ -1501,6 +1643,9 @@ class VoiceBank(_Windowed):
         self.root = _build(list(inputs))
         if isinstance(self.root, _LadderNode):
             self.root.is_root = True
+        for node in self._nodes():
+            if isinstance(node, _NoiseNode):
+                node.bank = weakref.ref(self)        # (NoisePE.advance settles an open window through it)
         self.mix_windows = False     # windows at the level of the mix whatever the root (set_mix_windows)
         self.request_dependent = any(node._REQUEST_DEPENDENT for node in self._nodes())     # (a pure sawtooth: no windows)
         self._reset_windows(BANK_WINDOW_FIRST)       # win.buf: the mixed window (Snippet), win.undo: [(node, snapshot)]
