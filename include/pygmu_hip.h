@@ -440,6 +440,27 @@ int pgx_channel_adapt(float *out, const float *in, int64_t n, int src_channels, 
  * panned to stereo; azimuth in degrees, clipped to +-90; azimuth_stream: per-frame float32 or NULL. */
 int pgx_pan(float *out, const float *in, int64_t n, int src_channels, float azimuth,
             const float *azimuth_stream, int constant_power);
+/* Panned voices of a bank (voice_bank.py).  One device function evaluates a pan gain for pgx_pan and the three entries below.
+ * pgx_pan_gains: gains[v] = {lg, rg} of azimuth[v] (device [batch], degrees) as pgx_pan evaluates them for a scalar
+ * azimuth -- once, when a bank is built.  batch <= 0: PGX_OK, nothing launched.  A null pointer: PGX_ERR_INVALID. */
+int pgx_pan_gains(float *gains /* [batch][2] */, const float *azimuth /* [batch] */, int batch, int constant_power);
+/* pgx_pan with the voice in the grid.  in: `batch` rows of n * src_channels float32, in_stride elements apart (>= n *
+ * src_channels);  out: `batch` rows of n * 2, out_stride apart (>= n * 2).  Exactly one of gains (device [batch][2] from
+ * pgx_pan_gains: scalar azimuths) and azimuth_stream (`batch` rows of n float32, az_stride elements apart, >= n) is non-null.
+ * Row v holds what pgx_pan(row v, azimuth v / stream row v) gives, bit for bit.
+ * n <= 0 or batch <= 0: PGX_OK, nothing launched.  A null out / in, src_channels outside 1 .. 128, a stride below its row,
+ * both or neither of gains / azimuth_stream, batch > 65535: PGX_ERR_INVALID, nothing launched. */
+int pgx_pan_bank(float *out, int64_t out_stride, const float *in, int64_t in_stride, int batch, int64_t n,
+                 int src_channels, const float *gains, const float *azimuth_stream, int64_t az_stride,
+                 int constant_power);
+/* out (n, 2) = sum over the voices of pgx_pan(voice): out[f][c] = sum_b float32(mono_b[f] * g_b,c[f]), mono the float32
+ * mean of the frame's src_channels, products rounded to float32, added in float32 in voice order starting from voice 0's
+ * product -- identical to pgx_pan per voice + pgx_mix_batch, without the [batch][n][2] layer.  in, in_stride (rows of a
+ * window allowed), gains, azimuth_stream, az_stride as for pgx_pan_bank; the voice is not in the grid: any batch.
+ * n <= 0 or batch <= 0: PGX_OK, nothing launched.  A null out / in, src_channels outside 1 .. 128, a stride below its row,
+ * both or neither of gains / azimuth_stream: PGX_ERR_INVALID, nothing launched. */
+int pgx_pan_mix_batch(float *out /* [n][2] */, const float *in, int64_t in_stride, int batch, int64_t n, int src_channels,
+                      const float *gains, const float *azimuth_stream, int64_t az_stride, int constant_power);
 /* out[i] = float32 mean of frame i's channels (the mono mix SpatialHRTF convolves, spatial_pe.py:483) */
 int pgx_mono_mean(float *out, const float *in, int64_t n, int src_channels);
 

@@ -466,26 +466,123 @@ k_channel_adapt(float *out, const float *in, int64_t n, int src_ch, int out_ch) 
     }
 }
 
+// The one expression for a pan gain in the library (k_pan, k_pan_gains, k_pan_bank, k_pan_mix_batch).
 // mode 0: linear (L = 1 - pan, R = pan, pan = (az + 90) / 180); 1: constant power (cos / sin of (az + 90) / 2 deg)
+__device__ __forceinline__ void pan_gains(float az, int mode, float &lg, float &rg) {
+    az = az < -90.0f ? -90.0f : (az > 90.0f ? 90.0f : az);
+    if (mode == 0) {
+        const float pan = (az + 90.0f) / 180.0f;
+        lg = 1.0f - pan;
+        rg = pan;
+    } else {
+        const float ang = ((az + 90.0f) / 2.0f) * (float)(3.141592653589793 / 180.0);   // np.deg2rad in float32
+        lg = cosf(ang);
+        rg = sinf(ang);
+    }
+}
+
 __global__ void __launch_bounds__(kBlock)
 k_pan(float *out, const float *in, int64_t n, int src_ch, float az_scalar, const float *az_stream, int mode) {
     const int64_t stride = (int64_t)gridDim.x * kBlock;
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
         const float mono = row_mean(in + i * src_ch, 0, src_ch);
-        float az = az_stream ? az_stream[i] : az_scalar;
-        az = az < -90.0f ? -90.0f : (az > 90.0f ? 90.0f : az);
         float lg, rg;
-        if (mode == 0) {
-            const float pan = (az + 90.0f) / 180.0f;
-            lg = 1.0f - pan;
-            rg = pan;
-        } else {
-            const float ang = ((az + 90.0f) / 2.0f) * (float)(3.141592653589793 / 180.0);   // np.deg2rad in float32
-            lg = cosf(ang);
-            rg = sinf(ang);
-        }
+        pan_gains(az_stream ? az_stream[i] : az_scalar, mode, lg, rg);
         out[i * 2 + 0] = mono * lg;
         out[i * 2 + 1] = mono * rg;
+    }
+}
+
+// gains[v] = {lg, rg} of voice v's scalar azimuth: evaluated once per bank, so that a scalar pan costs the kernels below
+// no transcendental per frame.  (Two ordinary vector stores per lane.)
+__global__ void __launch_bounds__(kBlock) k_pan_gains(float *gains, const float *azimuth, int batch, int mode) {
+    const int v = blockIdx.x * kBlock + threadIdx.x;
+    if (v >= batch) return;
+    float lg, rg;
+    pan_gains(azimuth[v], mode, lg, rg);
+    gains[2 * v + 0] = lg;
+    gains[2 * v + 1] = rg;
+}
+
+// k_pan with the voice in the grid (blockIdx.y): row v of `out` is k_pan over row v of `in`, its gains either the pair
+// k_pan_gains made of the voice's scalar azimuth or evaluated per frame from the voice's row of `az`.
+__global__ void __launch_bounds__(kBlock)
+k_pan_bank(float *out, int64_t out_stride, const float *in, int64_t in_stride, int64_t n, int src_ch, const float *gains,
+           const float *az, int64_t az_stride, int mode) {
+    const int v = blockIdx.y;
+    const float *x = in + (int64_t)v * in_stride;
+    float *y = out + (int64_t)v * out_stride;
+    float lg = 0.0f, rg = 0.0f;
+    if (gains) { lg = gains[2 * v + 0]; rg = gains[2 * v + 1]; }
+    else az += (int64_t)v * az_stride;
+    const int64_t stride = (int64_t)gridDim.x * kBlock;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
+        const float mono = row_mean(x + i * src_ch, 0, src_ch);
+        if (!gains) pan_gains(az[i], mode, lg, rg);
+        y[i * 2 + 0] = mono * lg;
+        y[i * 2 + 1] = mono * rg;
+    }
+}
+
+// out[f] = sum_b {float32(mono_b[f] * lg_b[f]), float32(mono_b[f] * rg_b[f])}: SpatialLinear / SpatialConstantPower voices
+// fused into the mix (k_pan per voice, then k_mix_batch).  Each product is rounded to float32 before the ordered float32
+// addition, the sum starts from voice 0's product (the sign of a zero survives), exactly as when the two kernels run
+// one after the other.  One thread per frame carries both channels' sums, so a voice's sample is loaded once.
+// (U voices of one frame, gain_mix_chunk's pattern and reason: every load of the chunk is issued before the first
+// product -- a lane's additions are ordered, so what keeps HBM busy is the number of loads in flight per lane.  PARTIAL:
+// the batch ends inside the chunk; the loads stay unconditional in form (predicated).  MONO: src_ch == 1, the voice's
+// sample is one load; else row_mean over the frame's channels.  STREAM: a row of azimuths per voice, else {lg, rg}.)
+template <int U, bool FIRST, bool PARTIAL, bool MONO, bool STREAM>
+__device__ __forceinline__ void pan_mix_chunk(float &accl, float &accr, const float *in, int64_t in_stride, int64_t f,
+                                              int src_ch, const float *gains, const float *az, int64_t az_stride,
+                                              int mode, int b, int batch) {
+    float xv[U], lv[U], rv[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        const bool on = !PARTIAL || b + u < batch;
+        const float *row = in + (int64_t)(b + u) * in_stride + f * src_ch;
+        if (MONO) xv[u] = on ? row[0] : 0.0f;
+        else xv[u] = on ? row_mean(row, 0, src_ch) : 0.0f;
+        if (STREAM) {
+            lv[u] = on ? az[(int64_t)(b + u) * az_stride + f] : 0.0f;      // (the azimuth: the gains are made of it below)
+        } else {
+            lv[u] = on ? gains[2 * (b + u) + 0] : 0.0f;
+            rv[u] = on ? gains[2 * (b + u) + 1] : 0.0f;
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        float lg, rg;
+        if (STREAM) pan_gains(lv[u], mode, lg, rg);
+        else { lg = lv[u]; rg = rv[u]; }
+        const float pl = xv[u] * lg, pr = xv[u] * rg;
+        if (FIRST && u == 0) { accl = pl; accr = pr; }
+        else if (!PARTIAL || b + u < batch) { accl = accl + pl; accr = accr + pr; }
+    }
+}
+
+template <bool MONO, bool STREAM>
+__global__ void __launch_bounds__(kBlock)
+k_pan_mix_batch(float *out, const float *in, int64_t in_stride, int batch, int64_t n, int src_ch, const float *gains,
+                const float *az, int64_t az_stride, int mode) {
+    // (a frame of several channels is several loads per voice already, on row_mean's eight running sums: 4 voices of
+    // those at a time -- 32 of them spill)
+    constexpr int U = MONO ? 32 : 4;
+    const int64_t stride = (int64_t)gridDim.x * kBlock;
+    for (int64_t f = (int64_t)blockIdx.x * kBlock + threadIdx.x; f < n; f += stride) {
+        float accl, accr;
+        int b = 0;
+        if (batch >= U) {
+            pan_mix_chunk<U, true, false, MONO, STREAM>(accl, accr, in, in_stride, f, src_ch, gains, az, az_stride, mode, 0, batch);
+            for (b = U; b + U <= batch; b += U)
+                pan_mix_chunk<U, false, false, MONO, STREAM>(accl, accr, in, in_stride, f, src_ch, gains, az, az_stride, mode, b, batch);
+            if (b < batch)
+                pan_mix_chunk<U, false, true, MONO, STREAM>(accl, accr, in, in_stride, f, src_ch, gains, az, az_stride, mode, b, batch);
+        } else {
+            pan_mix_chunk<U, true, true, MONO, STREAM>(accl, accr, in, in_stride, f, src_ch, gains, az, az_stride, mode, 0, batch);
+        }
+        out[f * 2 + 0] = accl;
+        out[f * 2 + 1] = accr;
     }
 }
 
@@ -520,6 +617,58 @@ int pgx_pan(float *out, const float *in, int64_t n, int src_channels, float azim
     hipLaunchKernelGGL(k_pan, dim3(pgx::grid_for(n, kBlock)), dim3(kBlock), 0, pgx::stream(), out, in, n,
                        src_channels, azimuth, azimuth_stream, constant_power ? 1 : 0);
     PGX_LAUNCH_CHECK("k_pan");
+    return PGX_OK;
+}
+
+int pgx_pan_gains(float *gains, const float *azimuth, int batch, int constant_power) {
+    PGX_REQUIRE_INIT();
+    if (batch <= 0) return PGX_OK;
+    PGX_CHECK_ARG(gains && azimuth, "pgx_pan_gains: bad argument");
+    hipLaunchKernelGGL(k_pan_gains, dim3(pgx::grid_for(batch, kBlock)), dim3(kBlock), 0, pgx::stream(), gains, azimuth,
+                       batch, constant_power ? 1 : 0);
+    PGX_LAUNCH_CHECK("k_pan_gains");
+    return PGX_OK;
+}
+
+int pgx_pan_bank(float *out, int64_t out_stride, const float *in, int64_t in_stride, int batch, int64_t n,
+                 int src_channels, const float *gains, const float *azimuth_stream, int64_t az_stride,
+                 int constant_power) {
+    PGX_REQUIRE_INIT();
+    if (n <= 0 || batch <= 0) return PGX_OK;
+    PGX_CHECK_ARG(out && in, "pgx_pan_bank: bad argument");
+    PGX_CHECK_ARG(src_channels >= 1 && src_channels <= kRowMeanMax, "pgx_pan_bank: source channels outside 1 .. 128");
+    PGX_CHECK_ARG((gains != nullptr) != (azimuth_stream != nullptr),
+                  "pgx_pan_bank: exactly one of gains and azimuth_stream");
+    PGX_CHECK_ARG(out_stride >= n * 2 && in_stride >= n * src_channels && (!azimuth_stream || az_stride >= n),
+                  "pgx_pan_bank: stride too small");
+    PGX_CHECK_ARG(batch <= 65535, "pgx_pan_bank: batch too large");
+    hipLaunchKernelGGL(k_pan_bank, dim3(pgx::grid_for(n, kBlock), batch), dim3(kBlock), 0, pgx::stream(), out, out_stride,
+                       in, in_stride, n, src_channels, gains, azimuth_stream, az_stride, constant_power ? 1 : 0);
+    PGX_LAUNCH_CHECK("k_pan_bank");
+    return PGX_OK;
+}
+
+int pgx_pan_mix_batch(float *out, const float *in, int64_t in_stride, int batch, int64_t n, int src_channels,
+                      const float *gains, const float *azimuth_stream, int64_t az_stride, int constant_power) {
+    PGX_REQUIRE_INIT();
+    if (n <= 0 || batch <= 0) return PGX_OK;
+    PGX_CHECK_ARG(out && in, "pgx_pan_mix_batch: bad argument");
+    PGX_CHECK_ARG(src_channels >= 1 && src_channels <= kRowMeanMax,
+                  "pgx_pan_mix_batch: source channels outside 1 .. 128");
+    PGX_CHECK_ARG((gains != nullptr) != (azimuth_stream != nullptr),
+                  "pgx_pan_mix_batch: exactly one of gains and azimuth_stream");
+    PGX_CHECK_ARG(in_stride >= n * src_channels && (!azimuth_stream || az_stride >= n),
+                  "pgx_pan_mix_batch: stride too small");
+    const dim3 grid(pgx::grid_for(n, kBlock)), block(kBlock);
+    const int mode = constant_power ? 1 : 0;
+    const bool mono = src_channels == 1;
+#define PGX_PAN_MIX(MONO, STREAM)                                                                                   \
+    hipLaunchKernelGGL((k_pan_mix_batch<MONO, STREAM>), grid, block, 0, pgx::stream(), out, in, in_stride, batch, n,  \
+                       src_channels, gains, azimuth_stream, az_stride, mode)
+    if (azimuth_stream) { if (mono) PGX_PAN_MIX(true, true); else PGX_PAN_MIX(false, true); }
+    else { if (mono) PGX_PAN_MIX(true, false); else PGX_PAN_MIX(false, false); }
+#undef PGX_PAN_MIX
+    PGX_LAUNCH_CHECK("k_pan_mix_batch");
     return PGX_OK;
 }
 

@@ -213,6 +213,7 @@ class SpatialPE(ProcessingElement):
 
     source = property(lambda self: self._source)
     method = property(lambda self: self._method)
+    _azimuth = property(lambda self: getattr(self._method, "azimuth", None))    # (voice_bank._Kind.children reads the PE)
 
     def inputs(self) -> list[ProcessingElement]:
         return [self._source, *self._method.inputs()]

@@ -16,8 +16,21 @@ AnalogOscPE (scalar parameters, or
 single-channel PEs of batchable classes), BiquadPE (constant coefficients, or cutoff and / or Q driven by single-channel
 PEs of batchable classes), LadderPE (scalar controls), CombPE (scalar controls), GainPE (constant or PE gain), TransformPE
 (a chain lowered to pgx_transform), AdsrGatedPE, PeriodicGate, SVFilterPE (scalar frequency and Q), AdsrTriggeredPE,
-PeriodicTrigger.
+PeriodicTrigger, SpatialPE (SpatialLinear / SpatialConstantPower with a scalar azimuth or a single-channel PE of a batchable
+class; SpatialAdapter).
 Anything else -> `try_build_bank` returns None and MixPE falls back to per-input rendering.
+
+Panned voices (_PanNode): a voice that ends in SpatialPE(voice, method=SpatialConstantPower(azimuth=a_i)) -- each voice at its
+place in the stereo field -- is a kind of its own, key ("pan", method class, azimuth is a PE, source[, azimuth]); the scalar
+azimuths are per-voice data, turned into {lg, rg}[K] ONCE when the node is built (pgx_pan_gains: the device function pgx_pan
+evaluates, so no transcendental per frame afterwards); a PE azimuth is a batched level of (n, 1) streams rendered first.  The
+node carries nothing.  As the root it is ONE launch per block, pgx_pan_mix_batch: every voice's mono sample is read once,
+multiplied by its two gains (each product rounded to float32) and added in voice order into the mix's (n, 2) block -- the
+additions of pgx_pan per voice followed by the mix, bit for bit, without the [K][n][2] layer.  Under another PE -- GainPE(
+SpatialPE(...), 0.5) -- it is a level like any other: pgx_pan_bank, pgx_pan with the voice in the grid.  SpatialAdapter
+(_AdaptNode) is one pgx_channel_adapt over the stacked K * n frames.  SpatialHRTF carries a convolution tail and is not
+batched; voices whose methods differ in class, that mix scalar and PE azimuths, or that share an azimuth PE are not one bank.
+Banked from MIN_VOICES voices on (measured: tools/pan_bank_probe.py -- the bank wins from 4 voices at both block lengths).
 
 Percussive voices: a constant SVFilterPE is a level of its own (pgx_svf_bank, _SvfNode: pgx_svf's plan with the voice in
 the grid, the host's nine constants per voice; an SVFilterPE with a PE parameter stays per voice), and
@@ -81,6 +94,7 @@ from .periodic_trigger import PeriodicTrigger
 from .processing_element import ProcessingElement
 from .sine_pe import SinePE
 from .snippet import Snippet
+from .spatial_pe import SpatialAdapter, SpatialConstantPower, SpatialLinear, SpatialPE
 from .super_saw_pe import SuperSawPE
 from .svfilter_pe import _SVF_MODE_INDEX, SVFilterPE, svf_coefficients
 from .transform_pe import TransformPE
@@ -145,6 +159,8 @@ LADDER_WINDOW_MAX = int(os.environ.get("PGX_LADDER_WINDOW_MAX", "32"))
 LADDER_WINDOW_FRAMES = int(os.environ.get("PGX_LADDER_WINDOW_FRAMES", str(1 << 21)))   # ... and at most this many frames
 PREFETCH_LADDER_INPUT = True
 PREFETCH_SUPERSAW_VOICES = True   # small SuperSaw banks under the mix: oscillators one block ahead (VoiceBank._supersaw_pipelined)  # _LadderNode: next block's oscillators beside this block's ladder
+FUSED_PAN_MIX = True          # a _PanNode root: pan and mix in ONE launch (pgx_pan_mix_batch), no [K][n][2] layer (False: pgx_pan_bank
+                              # + pgx_mix_batch, the same samples -- what tools/pan_bank_probe.py compares it with)
 FUSED_VOICE_MIN = 128        # voices (one workgroup each) from which BlitSaw -> Biquad runs as one launch
 SEGMENTED_CHAIN_MAX = int(os.environ.get("PGX_BBW_MAX_BATCH", "256"))
 SEGMENTED_CHAIN = True       # ... and smaller banks (4 .. 256 voices: a rank's share of C5) as one launch in concurrent time
@@ -1472,6 +1488,69 @@ class _GainNode(_Node):
         return out
 
 
+class _PanNode(_Node):
+    """Bank of SpatialPEs under SpatialLinear or SpatialConstantPower (one class per bank): pgx_pan with the voice in the
+    grid.  Scalar azimuths: uploaded once and turned into `gains` [K][2] by pgx_pan_gains when the node is built -- the
+    device function pgx_pan evaluates, so no transcendental per frame afterwards.  PE azimuths: a child level of (n, 1)
+    streams, the gains evaluated per frame.  Nothing is carried.  As a level: `render`, one pgx_pan_bank.  As the root:
+    `render_mix`, one pgx_pan_mix_batch straight into the mix's (n, 2) block."""
+
+    def __init__(self, pes, children):
+        super().__init__(pes, children)
+        self.mode = int(pes[0]._method._constant_power)
+        self.gains = None
+        if "azimuth" not in children:
+            self.azimuths = DeviceBuffer.from_host(np.array([float(pe._azimuth) for pe in pes], dtype=np.float32))
+            self.gains = DeviceBuffer((self.k, 2), np.float32)
+            check(lib().pgx_pan_gains(self.gains.ptr, self.azimuths.ptr, self.k, self.mode), "pgx_pan_gains")
+
+    def channels(self):
+        return 2
+
+    def _render(self, start, n, mix: bool):
+        x = self.children["source"].render(start, n)
+        az = self.children["azimuth"].render(start, n) if self.gains is None else None
+        ch = x.shape[2]
+        # what both entries take behind `out`: the source rows, then the gains or the azimuth rows
+        rows = (x.ptr, getattr(x, "stride", n * ch), self.k, n, ch, ptr(self.gains), ptr(az), getattr(az, "stride", n),
+                self.mode)
+        if mix:
+            out = DeviceBuffer((n, 2), np.float32)
+            check(lib().pgx_pan_mix_batch(out.ptr, *rows), "pgx_pan_mix_batch")
+        else:
+            out = DeviceBuffer((self.k, n, 2), np.float32)
+            check(lib().pgx_pan_bank(out.ptr, n * 2, *rows), "pgx_pan_bank")
+        return out
+
+    def render(self, start, n):
+        return self._render(start, n, mix=False)
+
+    def render_mix(self, start, n):
+        """The voices' mix as one (n, 2) block: what `render` followed by pgx_mix_batch gives, bit for bit."""
+        return self._render(start, n, mix=True)
+
+
+class _AdaptNode(_Node):
+    """Bank of SpatialPEs under SpatialAdapter(channels): one pgx_channel_adapt over the stacked K * n frames (frame by
+    frame: the voice does not matter).  As many channels as the source has: the source's buffer, as the method returns it."""
+
+    def __init__(self, pes, children):
+        super().__init__(pes, children)
+        self.out_ch = int(pes[0]._method.output_channels)
+
+    def channels(self):
+        return self.out_ch
+
+    def render(self, start, n):
+        x = self.children["source"].render(start, n)
+        ch = x.shape[2]
+        if ch == self.out_ch:
+            return x
+        out = DeviceBuffer((self.k, n, self.out_ch), np.float32)
+        check(lib().pgx_channel_adapt(out.ptr, x.ptr, self.k * n, ch, self.out_ch), "pgx_channel_adapt")
+        return out
+
+
 # ------------------------------------------------------------------------------------ builder
 def on_chip_mix_rule(pes) -> bool:
     """Host-only (no device, no bank): would a bank of these voices -- or of any subset of at least VOICE_TILES_MIN_VOICES of
@@ -1533,6 +1612,21 @@ def _biquad_batchable(pe) -> bool:
     return all(p.channel_count() == 1 for p, is_pe in ((pe._frequency, pe._freq_is_pe), (pe._q, pe._q_is_pe)) if is_pe)
 
 
+_PAN_METHODS = (SpatialLinear, SpatialConstantPower)
+
+
+def _spatial_panned(pe) -> bool:
+    return type(pe._method) in _PAN_METHODS
+
+
+def _spatial_batchable(pe) -> bool:
+    """SpatialAdapter; SpatialLinear / SpatialConstantPower with a scalar azimuth or an (n, 1) azimuth stream (the rule of
+    _osc_batchable: the PE itself takes channel 0 of anything).  Not SpatialHRTF: it carries a convolution tail."""
+    if type(pe._method) is SpatialAdapter:
+        return True
+    return _spatial_panned(pe) and (not _is_pe(pe._azimuth) or pe._azimuth.channel_count() == 1)
+
+
 def _transform_codes(pe):
     """The op codes of a TransformPE's device program -- what two voices must share to be one launch (their
     parameters may differ: _TransformNode) --, or None: a host callable, a chain that follows temperament.py's
@@ -1583,6 +1677,13 @@ _KINDS = (
           lambda pe: ADSR_TRIGGERED_MIN_VOICES),
     _Kind(GainPE, lambda pe: "gain_pe" if pe._gain_is_pe else "gain", _ALWAYS, None,
           (_SOURCE, ("gain", "_gain", lambda pe: pe._gain_is_pe)), _GainNode),
+    # (the method object decides: panners by class and by whether the azimuth is a PE -- the scalar azimuths are per-voice
+    # data --, the adapter by its channel count)
+    _Kind(SpatialPE, lambda pe: "pan" if _spatial_panned(pe) else "adapt", _spatial_batchable,
+          lambda pe: (type(pe._method).__name__, _is_pe(pe._azimuth)) if _spatial_panned(pe)
+          else (pe._method.output_channels,),
+          (_SOURCE, ("azimuth", "_azimuth", lambda pe: _spatial_panned(pe) and _is_pe(pe._azimuth))),
+          lambda pes, children: (_PanNode if _spatial_panned(pes[0]) else _AdaptNode)(pes, children)),
 )
 
 
@@ -1850,6 +1951,9 @@ class VoiceBank(_Windowed):
             if isinstance(gain, _AdsrGatedNode):
                 gain.mark_consumed(g)
             return Snippet(start, out)
+        if FUSED_PAN_MIX and isinstance(root, _PanNode):
+            # voices end in SpatialPE(x, <panner>): the pan fused into the mix, each voice's mono sample read once
+            return Snippet(start, root.render_mix(start, duration))
         stacked = root.render(start, duration)                   # [K][n][C], or rows of a window (_Rows)
         ch = stacked.shape[2]
         out = DeviceBuffer((duration, ch), np.float32)
