@@ -158,7 +158,7 @@ LADDER_WINDOW_FIRST = 2       # ... 2, then 4, 8, 16, 32 blocks (a lane of k_lad
 LADDER_WINDOW_MAX = int(os.environ.get("PGX_LADDER_WINDOW_MAX", "32"))
 LADDER_WINDOW_FRAMES = int(os.environ.get("PGX_LADDER_WINDOW_FRAMES", str(1 << 21)))   # ... and at most this many frames
 PREFETCH_LADDER_INPUT = True
-PREFETCH_SUPERSAW_VOICES = True   # small SuperSaw banks under the mix: oscillators one block ahead (VoiceBank._supersaw_pipelined)  # _LadderNode: next block's oscillators beside this block's ladder
+PREFETCH_SUPERSAW_VOICES = True   # small SuperSaw banks under the mix: oscillators one block ahead (_SuperSawNode.mix)  # _LadderNode: next block's oscillators beside this block's ladder
 FUSED_PAN_MIX = True          # a _PanNode root: pan and mix in ONE launch (pgx_pan_mix_batch), no [K][n][2] layer (False: pgx_pan_bank
                               # + pgx_mix_batch, the same samples -- what tools/pan_bank_probe.py compares it with)
 FUSED_VOICE_MIN = 128        # voices (one workgroup each) from which BlitSaw -> Biquad runs as one launch
@@ -200,6 +200,12 @@ class _Rows:
         self.ptr = buf.offset_ptr(offset * ch)
         self.shape = (k, n, ch)
         self.stride = total * ch
+
+
+def _rows(x, dense: int):
+    """(pointer, elements from voice to voice) of a [K][n][channels] DeviceBuffer -- `dense`: its rows lie back to back --
+    or of a _Rows; (None, dense) of None, a stream the kernel does not read."""
+    return ptr(x), getattr(x, "stride", dense)
 
 
 def _param_records(dtype, pes, fields) -> np.ndarray:
@@ -383,6 +389,27 @@ class _Node:
     def render(self, start: int, n: int) -> DeviceBuffer:
         """-> DeviceBuffer [K][n][channels] float32."""
         raise NotImplementedError
+
+    # ---- as the root of a VoiceBank: the node under the mix decides how its voices are added
+    def mixes_on_chip(self, n: int) -> bool:
+        """`mix` adds the voices of blocks of n frames on chip (pgx_voice_tiles): no [voices][frames] layer."""
+        return False
+
+    def mix(self, bank, start: int, n: int) -> DeviceBuffer:
+        """-> the MixPE's block (n, channels) for `bank`, the VoiceBank this node is the root of: the voices rendered, then
+        added in input order (pgx_mix_batch).  A node that can do better overrides this."""
+        stacked = self.render(start, n)                          # [K][n][C], or rows of a window (_Rows)
+        ch = stacked.shape[2]
+        out = DeviceBuffer((n, ch), np.float32)
+        check(lib().pgx_mix_batch(out.ptr, *_rows(stacked, n * ch), self.k, n * ch), "pgx_mix_batch")
+        return out
+
+    ws = None                    # a kernel's scratch: uint8, grown when a render needs more, never shrunk
+
+    def _scratch_of(self, need: int) -> DeviceBuffer:
+        if self.ws is None or self.ws.nbytes < need:
+            self.ws = DeviceBuffer((need,), np.uint8)
+        return self.ws
 
 
 class _SineNode(_Node):
@@ -632,8 +659,8 @@ class _BlitSawNode(_SawNode):
 class _SuperSawNode(_SawNode):
     """Bank of SuperSawPEs.  From FUSED_SUPERSAW_MIN instances on: one launch, voices summed on chip.  Below
     (a rank's share of a sharded mix): the oscillators of all instances in one launch (`_voices`), then the
-    ordered voice sum.  When the node feeds the bank's mix directly VoiceBank pipelines the two (see
-    VoiceBank._supersaw_pipelined): `ahead` then holds the oscillator samples of the block after the last one,
+    ordered voice sum.  When the node feeds the bank's mix directly the two are pipelined (see
+    `mix`): `ahead` then holds the oscillator samples of the block after the last one,
     or `ahead_bank` the bank's output for it."""
 
     def __init__(self, pes):
@@ -726,6 +753,40 @@ class _SuperSawNode(_SawNode):
             return out
         return self.sum_voices(self.take_voices(start, n), n)
 
+    def mix(self, bank, start, n):
+        """A bank of SuperSawPEs under the mix (a rank's share of a sharded mix: 64 instances at G = 8 -- or all 512).
+        The oscillators are the long pole and depend on nothing but time and two carried numbers each, so they
+        own the main stream, one block ahead: block k's mix (and, on the oscillator-by-oscillator path, its voice
+        sum) runs on the side stream beside block k+1's oscillators.  Nothing on the main stream ever waits for the side stream to catch up (the join at the end is
+        enqueued behind the oscillators, which outlast sum + mix): a cross-stream wait that has to wake a stalled
+        queue costs ~16 us on this part, a whole launch.  A pull that is not the next block copies the oscillator
+        states back (take_voices).  What follows on the library stream -- the all-reduce of this block, a read-back --
+        runs behind the next block's oscillators: one block of latency, no throughput."""
+        L = lib()
+        # (the voices-summed-on-chip bank + mix stay on one stream: with the bank one block ahead and the mix on the
+        # side stream a rank's share went from 60.5 to 64.3 us -- the fork / join packets cost more than the 5 us mix)
+        if not (PREFETCH_SUPERSAW_VOICES and n >= 4096
+                and (PIPELINE_FULL_SUPERSAW_BANK if self.fused() else not self.banked(n))
+                and not L.pgx_stream_is_forked()):
+            return super().mix(bank, start, n)
+        banked = self.banked(n)
+        # main stream: this block's oscillators (already there when the previous call rendered them ahead)
+        first = self.take_bank(start, n) if banked else self.take_voices(start, n)
+        check(L.pgx_stream_fork(), "pgx_stream_fork")                  # side stream: behind this block's oscillators
+        try:
+            stacked = first if banked else self.sum_voices(first, n)
+            ch = stacked.shape[2]
+            out = DeviceBuffer((n, ch), np.float32)
+            check(L.pgx_mix_batch(out.ptr, stacked.ptr, n * ch, self.k, n * ch), "pgx_mix_batch")
+            check(L.pgx_stream_select(0), "pgx_stream_select")
+            if banked:
+                self.render_bank_ahead(start + n, n)                   # main stream
+            else:
+                self.render_ahead(start + n, n)
+        finally:
+            check(L.pgx_stream_join(), "pgx_stream_join")
+        return out
+
 
 class _AnalogOscNode(_Node):
     """Bank of AnalogOscPEs of one waveform: pgx_analog_osc_bank, the PE's kernels with the voice in the grid.  Scalar
@@ -747,7 +808,6 @@ class _AnalogOscNode(_Node):
         self.stateful = bool(children)
         self.state = DeviceBuffer((self.k, 2), np.float64, zero=True) if self.stateful else None
         self.last_end = None
-        self.ws = None
         self._REQUEST_DEPENDENT = not self.stateful and self.wave == 1
 
     def reset(self):
@@ -762,9 +822,7 @@ class _AnalogOscNode(_Node):
         freq = self.children["frequency"].render(start, n) if "frequency" in self.children else None
         duty = self.children["duty"].render(start, n) if "duty" in self.children else None
         if self.stateful or self.wave:
-            need = L.pgx_analog_osc_bank_workspace_bytes(n, self.k)
-            if self.ws is None or self.ws.nbytes < need:
-                self.ws = DeviceBuffer((need,), np.uint8)
+            self._scratch_of(L.pgx_analog_osc_bank_workspace_bytes(n, self.k))
         out = DeviceBuffer((self.k, n, self.ch), np.float32)
         # the PE's own rule (AnalogOscPE._render): a render that does not continue the previous one starts over
         restart = self.stateful and (self.last_end is None or start != self.last_end)
@@ -776,7 +834,28 @@ class _AnalogOscNode(_Node):
         return out
 
 
-class _TransformNode(_Node):
+class _FedNode(_Node):
+    """A node fed by children["source"]: as many channels as the source has.  The filters among them carry `state`, float64
+    [K][channels][STATE_WIDTH], made (zeroed) by the first render -- which is where the channel count is known -- and zeroed
+    by reset()."""
+
+    STATE_WIDTH = 0              # numbers carried per voice and channel
+    state = None
+
+    def channels(self):
+        return self.children["source"].channels()
+
+    def _ensure_state(self, ch: int) -> None:
+        if self.state is None:
+            self.state = DeviceBuffer((self.k, ch, self.STATE_WIDTH), np.float64, zero=True)
+
+    def reset(self):
+        super().reset()
+        if self.state is not None:
+            self.state.zero_()
+
+
+class _TransformNode(_FedNode):
     """Bank of TransformPEs whose chains hold the same steps.  The same parameters in every voice (the PWM voice's
     Affine(0.4, 0.5)): one pgx_transform over the stacked K * n * channels elements.  Per-voice parameters (a pitch
     envelope's Affine(300, f_i)): pgx_transform_bank, one launch as well, each voice under its own ops."""
@@ -792,9 +871,6 @@ class _TransformNode(_Node):
                 table[i, j] = (code, 0, p0, p1)
         self.ops = DeviceBuffer.from_host(table.view(np.uint8))
 
-    def channels(self):
-        return self.children["source"].channels()
-
     def render(self, start, n):
         x = self.children["source"].render(start, n)
         k, _, ch = x.shape
@@ -806,8 +882,9 @@ class _TransformNode(_Node):
         return out
 
 
-class _BiquadNode(_Node):
+class _BiquadNode(_FedNode):
     _STATE = ("state",)
+    STATE_WIDTH = 2
 
     def __init__(self, pes, children):
         super().__init__(pes, children)
@@ -825,17 +902,7 @@ class _BiquadNode(_Node):
         self.tiles_ws = None
         self.entries_ahead = {}      # start -> (n, set): what the tiles of that block enter with, made behind the block before it
         self.tables = None           # per-voice powers of A (pgx_biquad_tables), made on first render
-        self.state = None
         self.state_alt = None        # (the time-segmented chain reads one buffer and writes the other)
-        self.ws = None
-
-    def reset(self):
-        super().reset()
-        if self.state is not None:
-            self.state.zero_()
-
-    def channels(self):
-        return self.children["source"].channels()
 
     def _chain_segments(self, n: int) -> int:
         """Time segments of the fused oscillator -> filter launch for a small bank, or 0: not that path."""
@@ -856,10 +923,6 @@ class _BiquadNode(_Node):
     def quiesce(self, keep=None):
         mine = self.entries_ahead.get(keep[0]) if keep is not None else None
         self.entries_ahead = {keep[0]: mine} if mine is not None and mine[0] == keep[1] else {}
-
-    def _ensure_state(self, ch: int) -> None:
-        if self.state is None:
-            self.state = DeviceBuffer((self.k, ch, 2), np.float64, zero=True)
 
     def _power_tables(self) -> DeviceBuffer:
         """Per-voice powers of A (pgx_biquad_tables), made on first use."""
@@ -911,6 +974,11 @@ class _BiquadNode(_Node):
         src.last_end = start + n
         return out
 
+    def mix(self, bank, start, n):
+        if self.mixes_on_chip(n):
+            return self.render_mix(start, n, streaming=bank.streaming)
+        return super().mix(bank, start, n)
+
     def _render_chain_segments(self, start, n):
         """A small bank (a rank's share of C5): oscillator -> filter as ONE launch in concurrent time segments instead of
         the segmented oscillator bank followed by the batched settled biquad (two kernels and the dispatch gap between
@@ -954,123 +1022,100 @@ class _BiquadNode(_Node):
         self._ensure_state(ch)
         tables = self._power_tables()
         need = L.pgx_biquad_workspace_bytes(self.k, n, ch, self.settle)
-        if need and (self.ws is None or self.ws.nbytes < need):
-            self.ws = DeviceBuffer((need,), np.uint8)
+        ws = self._scratch_of(need) if need else None
         out = DeviceBuffer((self.k, n, ch), np.float32)
         check(L.pgx_biquad_const(out.ptr, n * ch, x.ptr, n * ch, self.k, n, ch, self.coef.ptr,
-                                 tables.ptr, self.settle, self.state.ptr, ptr(self.ws) if need else None),
-              "pgx_biquad_const")
+                                 tables.ptr, self.settle, self.state.ptr, ptr(ws)), "pgx_biquad_const")
         return out
 
 
-class _BiquadVarNode(_Node):
-    """Bank of BiquadPEs whose cutoff and / or Q is a PE (the swept filter of a subtractive voice):
-    pgx_biquad_varying_bank, the PE's kernel with the voice in the grid.  The children's [K][n][ch] and [K][n][1] streams
-    first, then one call; mode, gain_db and the scalar of a parameter that is no PE are per voice (`params`, `gains`),
-    {x1, x2, y1, y2} is carried per voice and channel in `state`.  (No subclass of _BiquadNode: it takes none of the
-    on-chip mixes VoiceBank chooses by that class.)"""
+class _RowFilterNode(_FedNode):
+    """What _BiquadVarNode and _SvfNode share -- banks of a PE whose kernel takes the voice in the grid: `params`, one
+    BIQUAD_VAR_PARAMS record per voice as the PE's _render fills it (MODES: the PE's mode -> index table); `gains`, what
+    `_voice_gains` makes of each voice's 10^(gain_db / 40); the rule of the rows; the call, `_filter`."""
 
     _STATE = ("state",)
+    MODES = None
 
     def __init__(self, pes, children):
         super().__init__(pes, children)
         rec = np.zeros(self.k, dtype=_dev.BIQUAD_VAR_PARAMS)
-        gains = np.zeros((self.k, 2), dtype=np.float64)
-        for i, pe in enumerate(pes):          # (as BiquadPE._render fills them: 0.0 for a PE-valued parameter, never read)
+        for i, pe in enumerate(pes):          # (0.0 for a PE-valued parameter, never read)
             rec[i]["freq"] = 0.0 if pe._freq_is_pe else float(pe._frequency)
             rec[i]["q"] = 0.0 if pe._q_is_pe else float(pe._q)
             rec[i]["gain_db"] = float(pe._gain_db)
-            rec[i]["mode"] = _MODE_INDEX[pe._mode]
-            gain_a = 10.0 ** (pe._gain_db / 40.0)
-            gains[i] = (gain_a, math.sqrt(gain_a))
+            rec[i]["mode"] = self.MODES[pe._mode]
         self.params = _dev.upload_structs(rec)
-        self.gains = DeviceBuffer.from_host(gains)
-        self.state = None
-        self.ws = None
+        self.gains = DeviceBuffer.from_host(np.array([self._voice_gains(10.0 ** (pe._gain_db / 40.0)) for pe in pes],
+                                                     dtype=np.float64))
 
-    def reset(self):
-        super().reset()
-        if self.state is not None:
-            self.state.zero_()
-
-    def channels(self):
-        return self.children["source"].channels()
-
-    def render(self, start, n):
+    def _filter(self, entry: str, x, n, *between):
+        """-> out [K][n][ch] of lib().<entry>(out, out_stride, x, x_stride, K, n, ch, sr, params, gains, *between, state,
+        workspace).  From _walk_min_rows() rows (voices x channels) on no workspace is passed -- enough rows to give every
+        CU a workgroup: each row walked by one workgroup, one launch, the coefficients evaluated once, instead of the
+        segmented plan's reduce and apply."""
         L = lib()
-        x = self.children["source"].render(start, n)
-        freq = self.children["frequency"].render(start, n) if "frequency" in self.children else None
-        q = self.children["q"].render(start, n) if "q" in self.children else None
         ch = x.shape[2]
-        if self.state is None:
-            self.state = DeviceBuffer((self.k, ch, 4), np.float64, zero=True)
-        # enough rows to give every CU a workgroup: each row walked by one workgroup, one launch, the coefficients
-        # evaluated once (no workspace) instead of the segmented plan's reduce and apply
-        walk = self.k * ch >= BIQUAD_VAR_WALK_MIN_ROWS
+        self._ensure_state(ch)
+        walk = self.k * ch >= self._walk_min_rows()
         need = 0 if walk else self.k * L.pgx_scan2_workspace_bytes(n, ch)
-        if need and (self.ws is None or self.ws.nbytes < need):
-            self.ws = DeviceBuffer((need,), np.uint8)
+        ws = self._scratch_of(need) if need else None
         out = DeviceBuffer((self.k, n, ch), np.float32)
-        check(L.pgx_biquad_varying_bank(out.ptr, n * ch, x.ptr, getattr(x, "stride", n * ch), self.k, n, ch, self.sr,
-                                        self.params.ptr, self.gains.ptr, ptr(freq), getattr(freq, "stride", n),
-                                        ptr(q), getattr(q, "stride", n), self.state.ptr,
-                                        ptr(self.ws) if need else None), "pgx_biquad_varying_bank")
+        check(getattr(L, entry)(out.ptr, n * ch, *_rows(x, n * ch), self.k, n, ch, self.sr, self.params.ptr, self.gains.ptr,
+                                *between, self.state.ptr, ptr(ws)), entry)
         return out
 
 
-class _SvfNode(_Node):
+class _BiquadVarNode(_RowFilterNode):
+    """Bank of BiquadPEs whose cutoff and / or Q is a PE (the swept filter of a subtractive voice):
+    pgx_biquad_varying_bank, the PE's kernel with the voice in the grid.  The children's [K][n][ch] and [K][n][1] streams
+    first, then one call; mode, gain_db and the scalar of a parameter that is no PE are per voice (`params`, `gains`),
+    {x1, x2, y1, y2} is carried per voice and channel in `state`.  (No subclass of _BiquadNode: it takes none of the
+    on-chip mixes that class makes as the root.)"""
+
+    STATE_WIDTH = 4
+    MODES = _MODE_INDEX
+
+    @staticmethod
+    def _voice_gains(gain_a):
+        return gain_a, math.sqrt(gain_a)
+
+    def _walk_min_rows(self) -> int:
+        return BIQUAD_VAR_WALK_MIN_ROWS
+
+    def render(self, start, n):
+        x = self.children["source"].render(start, n)
+        freq = self.children["frequency"].render(start, n) if "frequency" in self.children else None
+        q = self.children["q"].render(start, n) if "q" in self.children else None
+        return self._filter("pgx_biquad_varying_bank", x, n, *_rows(freq, n), *_rows(q, n))
+
+
+class _SvfNode(_RowFilterNode):
     """Bank of SVFilterPEs with scalar frequency and Q: pgx_svf_bank, the PE's kernel with the voice in the grid.  Per voice:
     `params` and `gains` as SVFilterPE._render fills them (mode and gain_db are data, not part of the key) and `coef`, the
     nine numbers of svfilter_pe.svf_coefficients the PE uploads -- so each voice's samples and {s0, s1} are the PE's, bit for
     bit, while the node passes the workspace (the PE's segmented plan)."""
 
-    _STATE = ("state",)
+    STATE_WIDTH = 2
+    MODES = _SVF_MODE_INDEX
 
     def __init__(self, pes, children):
         super().__init__(pes, children)
-        rec = np.zeros(self.k, dtype=_dev.BIQUAD_VAR_PARAMS)
-        gains = np.zeros(self.k, dtype=np.float64)
-        coef = np.zeros((self.k, 9), dtype=np.float64)
-        for i, pe in enumerate(pes):
-            rec[i]["freq"] = float(pe._frequency)
-            rec[i]["q"] = float(pe._q)
-            rec[i]["gain_db"] = float(pe._gain_db)
-            rec[i]["mode"] = _SVF_MODE_INDEX[pe._mode]
-            gains[i] = 10.0 ** (pe._gain_db / 40.0)
-            coef[i] = svf_coefficients(pe._mode, pe._frequency, pe._q, pe._gain_db, self.sr)
-        self.params = _dev.upload_structs(rec)
-        self.gains = DeviceBuffer.from_host(gains)
-        self.coef = DeviceBuffer.from_host(coef)
-        self.state = None
-        self.ws = None
+        self.coef = DeviceBuffer.from_host(np.array([svf_coefficients(pe._mode, pe._frequency, pe._q, pe._gain_db, self.sr)
+                                                     for pe in pes], dtype=np.float64))
 
-    def reset(self):
-        super().reset()
-        if self.state is not None:
-            self.state.zero_()
+    @staticmethod
+    def _voice_gains(gain_a):
+        return gain_a
 
-    def channels(self):
-        return self.children["source"].channels()
+    def _walk_min_rows(self) -> int:
+        return SVF_WALK_MIN_ROWS
 
     def render(self, start, n):
-        L = lib()
-        x = self.children["source"].render(start, n)
-        ch = x.shape[2]
-        if self.state is None:
-            self.state = DeviceBuffer((self.k, ch, 2), np.float64, zero=True)
-        # (as _BiquadVarNode: enough rows to give every CU a workgroup -> each row walked by one workgroup in one launch)
-        walk = self.k * ch >= SVF_WALK_MIN_ROWS
-        need = 0 if walk else self.k * L.pgx_scan2_workspace_bytes(n, ch)
-        if need and (self.ws is None or self.ws.nbytes < need):
-            self.ws = DeviceBuffer((need,), np.uint8)
-        out = DeviceBuffer((self.k, n, ch), np.float32)
-        check(L.pgx_svf_bank(out.ptr, n * ch, x.ptr, getattr(x, "stride", n * ch), self.k, n, ch, self.sr,
-                             self.params.ptr, self.gains.ptr, None, 0, None, 0, self.coef.ptr, self.state.ptr,
-                             ptr(self.ws) if need else None), "pgx_svf_bank")
-        return out
+        return self._filter("pgx_svf_bank", self.children["source"].render(start, n), n, None, 0, None, 0, self.coef.ptr)
 
 
-class _LadderNode(_Windowed, _Node):
+class _LadderNode(_Windowed, _FedNode):
     """Bank of LadderPEs.  The ladder kernel is latency-bound (two waves per CU, most of the chip idle) and its
     input, a bank of scalar oscillators, is a pure function of time plus a few carried numbers -- so while block k
     goes through the ladder on the main stream, the oscillators of block k+1 are rendered on the side stream.
@@ -1078,6 +1123,7 @@ class _LadderNode(_Windowed, _Node):
     snapshot before it and copied back."""
 
     _STATE = ("state",)
+    STATE_WIDTH = 9
 
     def quiesce(self, keep=None):
         self._settle_window()
@@ -1086,8 +1132,6 @@ class _LadderNode(_Windowed, _Node):
     def __init__(self, pes, children):
         super().__init__(pes, children)
         self.params = _dev.upload_structs(_param_records(_dev.LADDER_PARAMS, pes, lambda pe: pe._scalar_params()))
-        self.state = None
-        self.ws = None
         settles = [pe._settle_frames() for pe in pes]
         self.settle = 0 if min(settles) == 0 else max(settles)     # one warm-up length for the batch
         self.accurate = max(pe._accurate_frames() for pe in pes) if self.settle else 0
@@ -1151,11 +1195,6 @@ class _LadderNode(_Windowed, _Node):
         self._reset_windows(LADDER_WINDOW_FIRST)
         self.ahead = None                            # (nothing to undo: the oscillators start over anyway)
         super().reset()
-        if self.state is not None:
-            self.state.zero_()
-
-    def channels(self):
-        return self.children["source"].channels()
 
     def _render_now(self, start, n):
         L = lib()
@@ -1165,8 +1204,7 @@ class _LadderNode(_Windowed, _Node):
         if x is None:
             x = src.render(start, n)
         ch = x.shape[2]
-        if self.state is None:
-            self.state = DeviceBuffer((self.k, ch, 9), np.float64, zero=True)
+        self._ensure_state(ch)
         out = DeviceBuffer((self.k, n, ch), np.float32)
         settle, accurate = self.settle, self.accurate
         if self.optimist is not None and n >= 8192:
@@ -1205,7 +1243,7 @@ class _LadderNode(_Windowed, _Node):
         return out
 
 
-class _CombNode(_Node):
+class _CombNode(_FedNode):
     """Bank of CombPEs with scalar frequency and feedback: every voice's D * C polyphase chains in one launch
     (two when the block is long enough to be cut into time segments), per-voice delay / feedback / ring."""
 
@@ -1218,7 +1256,6 @@ class _CombNode(_Node):
         self.d_min, self.d_max = int(rec["delay"].min()), int(rec["delay"].max())
         self.rows = int(rec["buffer_len"].max())
         self.ring = None
-        self.ws = None
         self.total = 0
         self.parity = 0
 
@@ -1228,9 +1265,6 @@ class _CombNode(_Node):
         # called from those
         self.ring = None
 
-    def channels(self):
-        return self.children["source"].channels()
-
     def render(self, start, n):
         L = lib()
         x = self.children["source"].render(start, n)
@@ -1239,12 +1273,11 @@ class _CombNode(_Node):
             self.ring = DeviceBuffer((self.k, 2, self.rows, ch), np.float64, zero=True)
             self.total, self.parity = 0, 0
         need = L.pgx_comb_workspace_bytes(self.k, n, ch, self.d_max, 0)
-        if need and (self.ws is None or self.ws.nbytes < need):
-            self.ws = DeviceBuffer((need,), np.uint8)
+        ws = self._scratch_of(need) if need else None
         out = DeviceBuffer((self.k, n, ch), np.float32)
         check(L.pgx_comb(out.ptr, n * ch, x.ptr, n * ch, self.k, n, ch, self.sr, self.params.ptr, self.d_min,
                          self.d_max, None, None, 1.0, 1, self.ring.ptr, self.rows, self.total, self.parity, None,
-                         ptr(self.ws) if need else None), "pgx_comb")
+                         ptr(ws)), "pgx_comb")
         self.total += n
         self.parity ^= 1
         return out
@@ -1294,7 +1327,6 @@ class _AdsrTriggeredNode(_Node):
         super().__init__(pes, children)
         self.params = _dev.upload_structs(_param_records(_dev.ADSR_PARAMS, pes, lambda pe: pe._adsr_params()))
         self.state = DeviceBuffer((self.k, 3), np.float64, zero=True)
-        self.ws = None
 
     def reset(self):
         super().reset()
@@ -1306,12 +1338,10 @@ class _AdsrTriggeredNode(_Node):
     def render(self, start, n):
         L = lib()
         trig = self.children["trigger"].render(start, n)
-        need = L.pgx_adsr_workspace_bytes(self.k, n)
-        if self.ws is None or self.ws.nbytes < need:
-            self.ws = DeviceBuffer((need,), np.uint8)
+        ws = self._scratch_of(L.pgx_adsr_workspace_bytes(self.k, n))
         out = DeviceBuffer((self.k, n, 1), np.float32)
-        check(L.pgx_adsr_triggered(out.ptr, n, trig.ptr, getattr(trig, "stride", n), self.k, start, n, self.params.ptr,
-                                   self.state.ptr, self.ws.ptr), "pgx_adsr_triggered")
+        check(L.pgx_adsr_triggered(out.ptr, n, *_rows(trig, n), self.k, start, n, self.params.ptr,
+                                   self.state.ptr, ws.ptr), "pgx_adsr_triggered")
         return out
 
 
@@ -1329,7 +1359,6 @@ class _AdsrGatedNode(_Node):
         super().__init__(pes, children)
         self.params = _dev.upload_structs(_param_records(_dev.ADSR_PARAMS, pes, lambda pe: pe._adsr_params()))
         self.state = DeviceBuffer((self.k, 3), np.float64, zero=True)
-        self.ws = None
         self.ahead = None            # _Ahead(envelopes; nothing to undo): render_ahead
         self.state_next = None       # ... which reads `state` and leaves the states after the block here
         self.ring = []               # ... into one of three envelope buffers of its own, used in turn: [buffer, event]
@@ -1338,11 +1367,9 @@ class _AdsrGatedNode(_Node):
 
     def _scratch(self, n):
         need = lib().pgx_adsr_workspace_bytes(self.k, n)
-        if self.ws is None or self.ws.nbytes < need:
-            if self.ahead is not None:                          # (the side stream may still be using the old one)
-                check(lib().pgx_stream_wait_detached(), "pgx_stream_wait_detached")
-            self.ws = DeviceBuffer((need,), np.uint8)
-        return self.ws
+        if self.ahead is not None and (self.ws is None or self.ws.nbytes < need):
+            check(lib().pgx_stream_wait_detached(), "pgx_stream_wait_detached")     # (the side stream may still be using the old one)
+        return self._scratch_of(need)
 
     def reset(self):
         self.forget_ahead()
@@ -1354,8 +1381,8 @@ class _AdsrGatedNode(_Node):
     # each, and their walk is a latency chain that leaves the machine to everybody else -- so block k+1's are walked
     # on the side stream while block k is mixed and block k+1's oscillators run; nobody waits for them until block
     # k+1's mix.  A pull that is not the next block puts the states back.
-    def forget_ahead(self, restore: bool = True) -> None:
-        """(restore: nothing to do -- a block rendered ahead reads `state` and writes `state_next`)"""
+    def forget_ahead(self) -> None:
+        """(nothing to put back: a block rendered ahead reads `state` and writes `state_next`)"""
         ahead, self.ahead = self.ahead, None
         if ahead is not None:
             check(lib().pgx_stream_wait_detached(), "pgx_stream_wait_detached")
@@ -1460,15 +1487,88 @@ class _AdsrGatedNode(_Node):
         return out
 
 
-class _GainNode(_Node):
+class _GainNode(_FedNode):
     def __init__(self, pes, children):
         super().__init__(pes, children)
         self.gains = None
         if "gain" not in children:
             self.gains = [float(np.float32(pe._gain)) for pe in pes]
 
-    def channels(self):
-        return self.children["source"].channels()
+    def mixes_on_chip(self, n):
+        """(a PE gain over the chain that mixes on chip -- `mix` also wants the gain to be one channel)"""
+        source = self.children["source"]
+        return self.gains is None and isinstance(source, _BiquadNode) and source.mixes_on_chip(n)
+
+    def mix(self, bank, start, n):
+        """Voices that end in GainPE(x, gain=<PE>): the per-voice multiply goes into the launch that adds the voices --
+        pgx_voice_tiles where the chain under the gain mixes on chip, else pgx_gain_mix_batch.  AdsrGatedPE(PeriodicGate)
+        envelopes (a fused gate) run one block ahead on the side stream from a stream's second block on."""
+        if self.gains is not None:
+            return super().mix(bank, start, n)
+        L = lib()
+        gain, source = self.children["gain"], self.children["source"]
+        gated = isinstance(gain, _AdsrGatedNode)
+        fused = gated and gain.fused_gate()
+        ahead = fused and ENVELOPE_AHEAD and n >= 1024 and not L.pgx_stream_is_forked()
+        walk_ahead = ahead and gain.last == (start - n, n)         # equal blocks, one after the other: the next one is walked ahead
+
+        def envelopes():
+            """-> (this block's gain rows, were they walked here?): the ones walked ahead while the last block was mixed (the
+            wait for the side stream is no wait by now), else -- a stream's first block, a seek, another kind of gain --
+            rendered now."""
+            g = gain.take_ahead(start, n) if ahead and gain.ahead is not None else None
+            return (g, False) if g is not None else (gain.render(start, n), True)
+
+        if self.mixes_on_chip(n) and gain.channels() == 1:
+            # GainPE(BiquadPE(BlitSawPE), gain=<PE>) voices: oscillator -> filter -> x gain -> mix in one kernel
+            # (pgx_voice_tiles).  The gains come first -- the kernel reads them -- so envelopes with a fused gate are
+            # walked one block ahead on the side stream, the next block's walk enqueued in front of this block's voices.
+            g, walked_here = envelopes()
+            if walk_ahead:
+                # (walked_here: this block's walk ran on the MAIN stream and left the states the next one starts from there --
+                # the side stream, which otherwise only waits for its envelope buffer's last reader, has to start behind it)
+                gain.render_ahead(start + n, n, edges_here=True, behind_main=walked_here)
+            out = source.render_mix(start, n, gain=g, streaming=walk_ahead)
+        else:
+            # fuse the per-voice multiply into the mix.  The gain sub-graph (envelopes: few, latency-bound waves) and the
+            # signal sub-graph (oscillators and filters: VALU-bound) share nothing, so they are enqueued on two streams
+            # and overlap.
+            if not fused:
+                check(L.pgx_stream_fork(), "pgx_stream_fork")
+                try:
+                    g = gain.render(start, n)
+                    check(L.pgx_stream_select(0), "pgx_stream_select")
+                    x = source.render(start, n)
+                finally:
+                    check(L.pgx_stream_join(), "pgx_stream_join")
+            elif ahead and gain.ahead is not None:
+                # this block's envelopes were walked while the last block was mixed.  (Multiplying by them in the chain's
+                # own kernel -- the mix then reads one [voices][frames] layer, not two: 35 -> 17 us -- made the oscillators
+                # depend on the envelopes; the next walk had to start in front of them and shared their SIMDs from the first
+                # tile: 512 voices 139 us per block against 137, 256 voices 91 against 90.  Removed.)
+                x = source.render(start, n)
+                g, _ = envelopes()                      # (a seek: walked now, behind the oscillators)
+            else:
+                # nothing was walked ahead: edge search first (parallel, short), then the walk detached on the side stream
+                try:
+                    g = gain.render(start, n, detach=True)
+                    x = source.render(start, n)
+                finally:
+                    if L.pgx_stream_is_forked():        # the fork happens inside the detached render
+                        check(L.pgx_stream_join(), "pgx_stream_join")
+            if walk_ahead:
+                # from a stream's second block on.  Between this block's oscillators and its mix: the side stream starts
+                # behind what the main stream holds at the fork.  Behind the mix the walk -- edge search, walk, a
+                # cross-stream wake-up: longer than the next block's oscillators -- became the critical path (a rank's 64
+                # voices: 66 -> 89 us per block); in front of the oscillators it shares the SIMDs with them from their
+                # first tile (66 -> 74 us; 512 voices 133 -> 143 us)
+                gain.render_ahead(start + n, n)
+            ch, gch = x.shape[2], g.shape[2]
+            out = DeviceBuffer((n, ch), np.float32)
+            check(L.pgx_gain_mix_batch(out.ptr, x.ptr, n * ch, g.ptr, n * gch, self.k, n, ch, gch), "pgx_gain_mix_batch")
+        if gated:
+            gain.mark_consumed(g)                       # (behind the launch that read them)
+        return out
 
     def render(self, start, n):
         L = lib()
@@ -1512,8 +1612,7 @@ class _PanNode(_Node):
         az = self.children["azimuth"].render(start, n) if self.gains is None else None
         ch = x.shape[2]
         # what both entries take behind `out`: the source rows, then the gains or the azimuth rows
-        rows = (x.ptr, getattr(x, "stride", n * ch), self.k, n, ch, ptr(self.gains), ptr(az), getattr(az, "stride", n),
-                self.mode)
+        rows = (*_rows(x, n * ch), self.k, n, ch, ptr(self.gains), *_rows(az, n), self.mode)
         if mix:
             out = DeviceBuffer((n, 2), np.float32)
             check(lib().pgx_pan_mix_batch(out.ptr, *rows), "pgx_pan_mix_batch")
@@ -1528,6 +1627,12 @@ class _PanNode(_Node):
     def render_mix(self, start, n):
         """The voices' mix as one (n, 2) block: what `render` followed by pgx_mix_batch gives, bit for bit."""
         return self._render(start, n, mix=True)
+
+    def mix(self, bank, start, n):
+        if FUSED_PAN_MIX:
+            # voices end in SpatialPE(x, <panner>): the pan fused into the mix, each voice's mono sample read once
+            return self.render_mix(start, n)
+        return super().mix(bank, start, n)
 
 
 class _AdaptNode(_Node):
@@ -1831,135 +1936,10 @@ class VoiceBank(_Windowed):
 
     def _mixes_on_chip(self, n: int) -> bool:
         """The voices of this bank are added on chip (pgx_voice_tiles) for blocks of n frames."""
-        root = self.root
-        if isinstance(root, _GainNode) and root.gains is None:
-            root = root.children["source"]
-        return isinstance(root, _BiquadNode) and root.mixes_on_chip(n)
-
-    def _supersaw_pipelined(self, start: int, n: int) -> Snippet:
-        """A bank of SuperSawPEs under the mix (a rank's share of a sharded mix: 64 instances at G = 8 -- or all 512).
-        The oscillators are the long pole and depend on nothing but time and two carried numbers each, so they
-        own the main stream, one block ahead: block k's mix (and, on the oscillator-by-oscillator path, its voice
-        sum) runs on the side stream beside block k+1's oscillators.  Nothing on the main stream ever waits for the side stream to catch up (the join at the end is
-        enqueued behind the oscillators, which outlast sum + mix): a cross-stream wait that has to wake a stalled
-        queue costs ~16 us on this part, a whole launch.  A pull that is not the next block copies the oscillator
-        states back (take_voices).  What follows on the library stream -- the all-reduce of this block, a read-back --
-        runs behind the next block's oscillators: one block of latency, no throughput."""
-        root, L = self.root, lib()
-        banked = root.banked(n)
-        # main stream: this block's oscillators (already there when the previous call rendered them ahead)
-        first = root.take_bank(start, n) if banked else root.take_voices(start, n)
-        check(L.pgx_stream_fork(), "pgx_stream_fork")                  # side stream: behind this block's oscillators
-        try:
-            stacked = first if banked else root.sum_voices(first, n)
-            ch = stacked.shape[2]
-            out = DeviceBuffer((n, ch), np.float32)
-            check(L.pgx_mix_batch(out.ptr, stacked.ptr, n * ch, self.k, n * ch), "pgx_mix_batch")
-            check(L.pgx_stream_select(0), "pgx_stream_select")
-            if banked:
-                root.render_bank_ahead(start + n, n)                   # main stream
-            else:
-                root.render_ahead(start + n, n)
-        finally:
-            check(L.pgx_stream_join(), "pgx_stream_join")
-        return Snippet(start, out)
+        return self.root.mixes_on_chip(n)
 
     def _render_mix_now(self, start: int, duration: int) -> Snippet:
-        root = self.root
-        # (the voices-summed-on-chip bank + mix stay on one stream: with the bank one block ahead and the mix on the
-        # side stream a rank's share went from 60.5 to 64.3 us -- the fork / join packets cost more than the 5 us mix)
-        if (PREFETCH_SUPERSAW_VOICES and isinstance(root, _SuperSawNode) and duration >= 4096
-                and (PIPELINE_FULL_SUPERSAW_BANK if root.fused() else not root.banked(duration))
-                and not lib().pgx_stream_is_forked()):
-            return self._supersaw_pipelined(start, duration)
-        if isinstance(root, _BiquadNode) and root.mixes_on_chip(duration):
-            return Snippet(start, root.render_mix(start, duration, streaming=self.streaming))
-        if (isinstance(root, _GainNode) and root.gains is None and isinstance(root.children["source"], _BiquadNode)
-                and root.children["source"].mixes_on_chip(duration) and root.children["gain"].channels() == 1):
-            # GainPE(BiquadPE(BlitSawPE), gain=<PE>) voices: oscillator -> filter -> x gain -> mix in one kernel
-            # (pgx_voice_tiles).  The gains come first -- the kernel reads them -- so envelopes with a fused gate are
-            # walked one block ahead on the side stream, the next block's walk enqueued in front of this block's voices.
-            L = lib()
-            gain, source = root.children["gain"], root.children["source"]
-            ahead = (isinstance(gain, _AdsrGatedNode) and gain.fused_gate() and ENVELOPE_AHEAD and duration >= 1024
-                     and not L.pgx_stream_is_forked())
-            g = None
-            if ahead:
-                streaming = gain.last == (start - duration, duration)      # equal blocks, one after the other
-                if gain.ahead is not None:
-                    g = gain.take_ahead(start, duration)
-            walked_here = g is None
-            if walked_here:
-                g = gain.render(start, duration)        # a stream's first block, a seek, another kind of gain: rendered now
-            if ahead and streaming:
-                # (walked_here: this block's walk ran on the MAIN stream and left the states the next one starts from there --
-                # the side stream, which otherwise only waits for its envelope buffer's last reader, has to start behind it)
-                gain.render_ahead(start + duration, duration, edges_here=True, behind_main=walked_here)
-            out = source.render_mix(start, duration, gain=g, streaming=ahead and streaming)
-            if isinstance(gain, _AdsrGatedNode):
-                gain.mark_consumed(g)
-            return Snippet(start, out)
-        if isinstance(root, _GainNode) and root.gains is None:
-            # voices end in GainPE(x, gain=<PE>): fuse the per-voice multiply into the mix.  The gain
-            # sub-graph (envelopes: few, latency-bound waves) and the signal sub-graph (oscillators and
-            # filters: VALU-bound) share nothing, so they are enqueued on two streams and overlap.
-            L = lib()
-            gain = root.children["gain"]
-            walk_ahead = False
-            if isinstance(gain, _AdsrGatedNode) and gain.fused_gate():
-                ahead_ok = ENVELOPE_AHEAD and duration >= 1024 and not L.pgx_stream_is_forked()
-                streaming = gain.last == (start - duration, duration)      # equal blocks, one after the other
-                source = root.children["source"]
-                if ahead_ok and gain.ahead is not None:
-                    # this block's envelopes were walked while the last block was mixed (the wait for the side stream is
-                    # no wait by now).  (Multiplying by them in the chain's own kernel -- the mix then reads one
-                    # [voices][frames] layer, not two: 35 -> 17 us -- made the oscillators depend on the envelopes; the next
-                    # walk had to start in front of them and shared their SIMDs from the first tile: 512 voices 139 us per
-                    # block against 137, 256 voices 91 against 90.  Removed.)
-                    x = source.render(start, duration)
-                    g = gain.take_ahead(start, duration)
-                    if g is None:                       # a seek: walked now, behind the oscillators
-                        g = gain.render(start, duration)
-                else:
-                    # edge search first (parallel, short), then the walk detached on the side stream
-                    try:
-                        g = gain.render(start, duration, detach=True)
-                        x = source.render(start, duration)
-                    finally:
-                        if L.pgx_stream_is_forked():        # the fork happens inside the detached render
-                            check(L.pgx_stream_join(), "pgx_stream_join")
-                walk_ahead = ahead_ok and streaming
-            else:
-                check(L.pgx_stream_fork(), "pgx_stream_fork")
-                try:
-                    g = gain.render(start, duration)
-                    check(L.pgx_stream_select(0), "pgx_stream_select")
-                    x = root.children["source"].render(start, duration)
-                finally:
-                    check(L.pgx_stream_join(), "pgx_stream_join")
-            if walk_ahead:
-                # from a stream's second block on.  Between this block's oscillators and its mix: the side stream starts
-                # behind what the main stream holds at the fork.  Behind the mix the walk -- edge search, walk, a
-                # cross-stream wake-up: longer than the next block's oscillators -- became the critical path (a rank's 64
-                # voices: 66 -> 89 us per block); in front of the oscillators it shares the SIMDs with them from their
-                # first tile (66 -> 74 us; 512 voices 133 -> 143 us)
-                gain.render_ahead(start + duration, duration)
-            ch, gch = x.shape[2], g.shape[2]
-            out = DeviceBuffer((duration, ch), np.float32)
-            check(lib().pgx_gain_mix_batch(out.ptr, x.ptr, duration * ch, g.ptr, duration * gch, self.k,
-                                           duration, ch, gch), "pgx_gain_mix_batch")
-            if isinstance(gain, _AdsrGatedNode):
-                gain.mark_consumed(g)
-            return Snippet(start, out)
-        if FUSED_PAN_MIX and isinstance(root, _PanNode):
-            # voices end in SpatialPE(x, <panner>): the pan fused into the mix, each voice's mono sample read once
-            return Snippet(start, root.render_mix(start, duration))
-        stacked = root.render(start, duration)                   # [K][n][C], or rows of a window (_Rows)
-        ch = stacked.shape[2]
-        out = DeviceBuffer((duration, ch), np.float32)
-        check(lib().pgx_mix_batch(out.ptr, stacked.ptr, getattr(stacked, "stride", duration * ch), self.k, duration * ch),
-              "pgx_mix_batch")
-        return Snippet(start, out)
+        return Snippet(start, self.root.mix(self, start, duration))
 
 
 def try_build_bank(inputs):

@@ -1,6 +1,6 @@
 """
 CPU: what a bank of NoisePE voices, of hi-hat voices and of voices swept by a FunctionGenPE launches -- pinned against a
-recorded trace, with the stand-ins of tests/test_voice_bank_trace.py (its Recorder, Library and buffers: no device).
+recorded trace, with the stand-ins of tests/bank_trace.py (its Recorder, Library and buffers: no device).
 
 Graphs, five voices each, the measured minimums set to 4:
     pink    NoisePE(seed=i, mode=PINK)
@@ -17,15 +17,11 @@ was built.
     python tests/test_noise_bank_trace.py --record        writes tests/golden/noise_bank_trace.json
 """
 
-import gc
-import json
 import os
-import sys
 
 import pytest
 
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from test_voice_bank_trace import install, launches      # noqa: E402
+from bank_trace import assert_matches, install, record_main, recorded, recorded_names, run
 
 FIXTURE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "noise_bank_trace.json")
 K = 5
@@ -57,33 +53,12 @@ def voices(pg, kind):
 
 
 def run_case(monkeypatch, name):
-    """-> (the canonical trace of case `name`, the index of its first pull)"""
+    """-> the canonical trace of case `name`."""
     import pygmu2_amd as pg
-    from pygmu2_amd import config, voice_bank
     kind, pulls = name.split("-")
     pulls, mix_windows = SCRIPTS[pulls]
-    rec = install(monkeypatch)
-    for minimum in MINIMUMS:
-        monkeypatch.setattr(voice_bank, minimum, 4)
-    monkeypatch.setattr(config, "_sample_rate", 48000)
-    bank = voice_bank.try_build_bank(voices(pg, kind))
-    assert bank is not None and bank.k == K
-    if mix_windows:
-        bank.set_mix_windows()
-    for pull in pulls:
-        rec.note("pull", *pull)
-        out = bank.render_mix(*pull)
-        rec.note("return", rec.name(out.dev.ptr), out.duration, out.channels, bool(out._bank_window))
-        del out
-    del bank
-    gc.collect()
-    rec.recording = False
-    return rec.entries
-
-
-def _recorded():
-    with open(FIXTURE) as f:
-        return {name: trace for name, trace in (json.loads(line) for line in f if line.strip())}
+    return run(monkeypatch, lambda: voices(pg, kind), pulls, switches={minimum: 4 for minimum in MINIMUMS},
+               mix_windows=mix_windows)
 
 
 def _renders(trace, entry_names):
@@ -99,12 +74,7 @@ def _renders(trace, entry_names):
 
 @pytest.mark.parametrize("name", CASES)
 def test_launch_trace(monkeypatch, name):
-    want = _recorded()[name]
-    got = json.loads(json.dumps(run_case(monkeypatch, name)))
-    a, b = launches(got), launches(want)
-    for i, (x, y) in enumerate(zip(a, b)):
-        assert x == y, f"{name}: entry {i} is {x}, recorded {y} (after {a[max(0, i - 3):i]})"
-    assert len(a) == len(b), f"{name}: {len(a)} entries, recorded {len(b)}"
+    assert_matches(name, run_case(monkeypatch, name), recorded(FIXTURE)[name])
 
 
 @pytest.mark.parametrize("pulls", list(SCRIPTS))
@@ -239,21 +209,8 @@ def np_any(values):
 
 
 def test_fixture_has_every_case_once():
-    with open(FIXTURE) as f:
-        names = [json.loads(line)[0] for line in f if line.strip()]
-    assert names == CASES
+    assert recorded_names(FIXTURE) == CASES
 
 
 if __name__ == "__main__":
-    if sys.argv[1:] != ["--record"]:
-        sys.exit(__doc__)
-    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-    with open(FIXTURE, "w") as f:
-        for case in CASES:
-            patch = pytest.MonkeyPatch()
-            try:
-                trace = run_case(patch, case)
-            finally:
-                patch.undo()
-            f.write(json.dumps([case, trace], separators=(",", ":")) + "\n")
-            print(case, len(trace))
+    record_main(FIXTURE, CASES, run_case)

@@ -1,6 +1,6 @@
 """
 CPU: what a bank of panned voices launches -- pinned against a recorded trace, with the stand-ins of
-tests/test_voice_bank_trace.py (its Recorder, Library and buffers: no device).
+tests/bank_trace.py (its Recorder, Library and buffers: no device).
 
 Graphs (tests/pan_cases.py), five voices each:
     scalar   SpatialPE(SinePE, SpatialConstantPower(azimuth=a_i))                       a _PanNode root, gains
@@ -16,17 +16,14 @@ decline rules of voice_bank's SpatialPE kind are asserted on _signature / try_bu
     python tests/test_pan_bank_trace.py --record        writes tests/golden/pan_bank_trace.json
 """
 
-import gc
-import json
 import os
 import sys
 
 import pytest
 
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(1, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))      # (oracle.golden_cases.S, run as a script)
 import pan_cases                                          # noqa: E402
-from test_voice_bank_trace import install, launches      # noqa: E402
+from bank_trace import assert_matches, install, record_main, recorded, recorded_names, run      # noqa: E402
 
 FIXTURE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "pan_bank_trace.json")
 K = pan_cases.K
@@ -42,27 +39,15 @@ def build_voices(kind, count=K):
 
 def run_case(monkeypatch, kind):
     """-> the canonical trace of case `kind`."""
-    from pygmu2_amd import config, voice_bank
-    rec = install(monkeypatch)
-    monkeypatch.setattr(config, "_sample_rate", pan_cases.SR)
-    bank = voice_bank.try_build_bank(build_voices(kind))
-    assert bank is not None and bank.k == K
-    assert type(bank.root).__name__ == pan_cases.ROOTS[kind]
-    for pull in PULLS:
-        rec.note("pull", *pull)
-        out = bank.render_mix(*pull)
-        rec.note("return", rec.name(out.dev.ptr), out.duration, out.channels, bool(out._bank_window))
-        assert (out.duration, out.channels) == (BLOCK, 2)
-        del out
-    del bank
-    gc.collect()
-    rec.recording = False
-    return rec.entries
+    assert pan_cases.SR == 48000                                  # (bank_trace.run's rate)
 
+    def built(bank):
+        assert type(bank.root).__name__ == pan_cases.ROOTS[kind]
 
-def _recorded():
-    with open(FIXTURE) as f:
-        return {name: trace for name, trace in (json.loads(line) for line in f if line.strip())}
+    trace = run(monkeypatch, lambda: build_voices(kind), PULLS, built=built)
+    returns = [e for e in trace if e[0] == "return"]              # [name, stream, pointer, frames, channels, window row?]
+    assert len(returns) == len(PULLS) and all((e[3], e[4]) == (BLOCK, 2) for e in returns)
+    return trace
 
 
 def _blocks(trace):
@@ -73,12 +58,7 @@ def _blocks(trace):
 
 @pytest.mark.parametrize("name", CASES)
 def test_launch_trace(monkeypatch, name):
-    want = _recorded()[name]
-    got = json.loads(json.dumps(run_case(monkeypatch, name)))
-    a, b = launches(got), launches(want)
-    for i, (x, y) in enumerate(zip(a, b)):
-        assert x == y, f"{name}: entry {i} is {x}, recorded {y} (after {a[max(0, i - 3):i]})"
-    assert len(a) == len(b), f"{name}: {len(a)} entries, recorded {len(b)}"
+    assert_matches(name, run_case(monkeypatch, name), recorded(FIXTURE)[name])
 
 
 @pytest.mark.parametrize("kind", ["scalar", "lfo"])
@@ -257,20 +237,8 @@ def test_the_probe_records_give_no_pan_minimum():
 
 
 def test_fixture_has_every_case_once():
-    with open(FIXTURE) as f:
-        names = [json.loads(line)[0] for line in f if line.strip()]
-    assert names == CASES
+    assert recorded_names(FIXTURE) == CASES
 
 
 if __name__ == "__main__":
-    if sys.argv[1:] != ["--record"]:
-        sys.exit(__doc__)
-    with open(FIXTURE, "w") as f:
-        for case in CASES:
-            patch = pytest.MonkeyPatch()
-            try:
-                trace = run_case(patch, case)
-            finally:
-                patch.undo()
-            f.write(json.dumps([case, trace], separators=(",", ":")) + "\n")
-            print(case, len(trace))
+    record_main(FIXTURE, CASES, run_case)

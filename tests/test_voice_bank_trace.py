@@ -1,201 +1,23 @@
 """
-CPU: what a voice bank launches, in which order, on which stream, with which buffers -- pinned against a recorded trace.
+CPU: what a voice bank launches, in which order, on which stream, with which buffers -- pinned against a recorded trace
+(tests/bank_trace.py: the stand-ins for the library and the buffers, the canonical form, what must match).
 
-voice_bank.py talks to the device through a handful of seams; with stand-ins there `try_build_bank(...).render_mix(...)`
-runs without a GPU and every call it would have made is written down:
-
-* the library (`voice_bank.lib()`, `_kernels.lib()`): every pgx_* call with the stream it lands on.  The stand-in keeps
-  the stream state itself (pgx_stream_fork / fork_after -> side stream 1, select, join / detach -> main stream 0) and
-  answers pgx_stream_is_forked from it.  Launches return 0.  The host-side queries are answered, not recorded:
-      pgx_*_segments(instances, ...)  -> 4 below 128 instances, else 1 (both the segmented and the one-segment paths occur)
-      pgx_*_bytes(...)                -> 65536
-      pgx_biquad_table_doubles()      -> 64
-      pgx_voice_tiles_max_warm()      -> 2048
-* the buffers (`DeviceBuffer` of voice_bank, device and _kernels): a subclass that allocates nothing.  Buffer number i has
-  the base address i << 40, so offset_ptr() and rows() work; from_host / upload are recorded as "h2d" with a short hash of
-  the bytes, zero_ / zero=True as "zero", the release (__del__) as "free".
-* the events (`device.Event`): "event_record".
-
-Canonical form: one entry per call, [name, stream, args...].  Which arguments are pointers comes from device._SIGNATURES;
-a pointer is written "b<k>+<byte offset>" with k the order in which its buffer first appears in the trace (not its
-allocation order: moving a lazy allocation changes nothing, aliasing and double-buffer swaps show).  Each pull of the
-script adds ["pull", start, frames] and ["return", pointer, frames, channels, row of a window?].  A buffer that is still
-alive after gc.collect() at the end of a case is written ["unreleased", "b<k>"].
-
-The launch entries must equal the recorded ones exactly.  No buffer may be released EARLIER than recorded (counted in
-entries in front of its release: an early return to the pool is how a side stream ends up reading a recycled block); a
-later release is reported (a warning) and wants an explanation.
+Cases: SuperSaw banks of every size class, the C4 (ladder) and C5 (BlitSaw -> Biquad x envelope) voices, comb, constant
+biquad, sine and constant-gain banks, each under the switches that change its path, over a script of windows, seeks,
+another block length and a reset.
 
     python tests/test_voice_bank_trace.py --record        writes tests/golden/voice_bank_trace.json
 """
 
-import functools
-import gc
-import hashlib
-import itertools
-import json
 import os
-import sys
-import warnings
 
-import numpy as np
 import pytest
+
+from bank_trace import assert_matches, launches, record_main, recorded, recorded_names, run
 
 FIXTURE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "voice_bank_trace.json")
 SWITCHES = ("BANK_WINDOWS", "LADDER_WINDOWS", "ENVELOPE_AHEAD", "PREFETCH_SUPERSAW_VOICES", "PREFETCH_LADDER_INPUT")
 ALL_OFF = {name: False for name in SWITCHES}
-BASE_SHIFT = 40
-_BASES = itertools.count(1)         # buffer numbers, never reused: a buffer that outlives its case is not mistaken
-
-
-class Recorder:
-    """The trace, the stream state and the address book of one case."""
-
-    def __init__(self, recording=True):
-        import ctypes
-        from pygmu2_amd import device
-        self.recording = recording
-        self.entries = []
-        self.stream = 0
-        self.forked = False
-        self.names = {}              # buffer / event number -> canonical name, in order of first appearance
-        self.alive = set()           # numbers of the buffers that exist
-        self.pointer_args = {name: [i for i, t in enumerate(args) if t is ctypes.c_void_p]
-                             for name, _, args in device._SIGNATURES}
-
-    def new_base(self) -> int:
-        return next(_BASES) << BASE_SHIFT
-
-    def name(self, address):
-        if address is None:
-            return None
-        base = address >> BASE_SHIFT
-        if base not in self.names:
-            self.names[base] = f"b{len(self.names)}"
-        return f"{self.names[base]}+{address & ((1 << BASE_SHIFT) - 1)}"
-
-    def note(self, what, *args):
-        if self.recording:
-            self.entries.append([what, self.stream, *args])
-
-    def released(self, address):
-        base = address >> BASE_SHIFT
-        if self.recording and base in self.names:        # (a buffer no call ever saw: nothing to say)
-            self.entries.append(["free", self.names[base]])
-
-
-class Library:
-    """Stands in for the ctypes library: attribute `pgx_<name>` is a function."""
-
-    def __init__(self, rec):
-        self._rec = rec
-
-    def pgx_stream_is_forked(self):
-        return 1 if self._rec.forked else 0
-
-    def _stream_call(self, name, forked, stream):
-        rec = self._rec
-
-        def call(*args):
-            rec.note(name, *[rec.name(a) if name == "pgx_stream_fork_after" else a for a in args])
-            rec.forked = forked
-            rec.stream = args[0] if stream is None else stream
-            return 0
-        return call
-
-    def __getattr__(self, name):
-        if not name.startswith("pgx_"):
-            raise AttributeError(name)
-        rec = self._rec
-        if name.endswith("_segments"):
-            fn = lambda instances, *rest: 4 if instances < 128 else 1
-        elif name.endswith("_bytes"):
-            fn = lambda *args: 65536
-        elif name == "pgx_biquad_table_doubles":
-            fn = lambda: 64
-        elif name == "pgx_voice_tiles_max_warm":
-            fn = lambda: 2048
-        elif name in ("pgx_stream_fork", "pgx_stream_fork_after"):
-            fn = self._stream_call(name, True, 1)
-        elif name == "pgx_stream_select":
-            fn = self._stream_call(name, True, None)
-        elif name in ("pgx_stream_join", "pgx_stream_detach"):
-            fn = self._stream_call(name, False, 0)
-        elif not rec.recording:
-            fn = lambda *args: 0
-        else:
-            pointers = rec.pointer_args[name]                   # KeyError: not a function of the C ABI
-
-            def fn(*args):
-                rec.entries.append([name, rec.stream, *[rec.name(a) if i in pointers else a for i, a in enumerate(args)]])
-                return 0
-        self.__dict__[name] = fn
-        return fn
-
-
-def install(monkeypatch, recording=True):
-    """Put the stand-ins in place (monkeypatch undoes it) -> the Recorder."""
-    from pygmu2_amd import _kernels, device, voice_bank
-    rec = Recorder(recording)
-    library = Library(rec)
-
-    class Buffer(device.DeviceBuffer):
-        __slots__ = ()
-
-        def __init__(self, shape, dtype=np.float32, *, zero=False):
-            self.shape = tuple(int(v) for v in shape) if isinstance(shape, (tuple, list)) else (int(shape),)
-            self.dtype = np.dtype(dtype)
-            self.nbytes = self.dtype.itemsize
-            for v in self.shape:
-                self.nbytes *= v
-            self.ptr = rec.new_base()
-            self._owner = True
-            rec.alive.add(self.ptr >> BASE_SHIFT)
-            if zero and self.nbytes:
-                rec.note("zero", rec.name(self.ptr))
-
-        @classmethod
-        def from_host(cls, array):
-            a = np.ascontiguousarray(array)
-            buf = cls(a.shape, a.dtype)
-            if a.nbytes:
-                rec.note("h2d", rec.name(buf.ptr), hashlib.sha1(a.tobytes()).hexdigest()[:8])
-            return buf
-
-        def upload(self, array):
-            a = np.ascontiguousarray(array, dtype=self.dtype)
-            assert a.nbytes == self.nbytes
-            if a.nbytes:
-                rec.note("h2d", rec.name(self.ptr), hashlib.sha1(a.tobytes()).hexdigest()[:8])
-
-        def zero_(self):
-            if self.nbytes:
-                rec.note("zero", rec.name(self.ptr))
-
-        def to_host(self):
-            raise AssertionError("a bank does not read back")
-
-        begin_to_host = to_host
-
-        def __del__(self):
-            if getattr(self, "_owner", False) is True and self.ptr:
-                rec.alive.discard(self.ptr >> BASE_SHIFT)
-                rec.released(self.ptr)
-            self.ptr = 0
-
-    class Event:
-        def __init__(self):
-            self.ptr = rec.new_base()
-
-        def record(self):
-            rec.note("event_record", rec.name(self.ptr))
-
-    for module in (voice_bank, _kernels):
-        monkeypatch.setattr(module, "lib", lambda: library)
-        monkeypatch.setattr(module, "DeviceBuffer", Buffer)
-    monkeypatch.setattr(device, "DeviceBuffer", Buffer)
-    monkeypatch.setattr(device, "Event", Event)
-    return rec
 
 
 # ------------------------------------------------------------------------------------------------------------ cases
@@ -296,89 +118,23 @@ _case("supersaw", 260, [("pgx_supersaw_bank_seg", 0)], pulls="SHORT", tag="short
 def run_case(monkeypatch, name):
     """-> the canonical trace of case `name`."""
     import pygmu2_amd as pg
-    from pygmu2_amd import config, voice_bank
     kind, count, switches, mix_windows, pulls, _ = CASES[name]
-    rec = install(monkeypatch)
-    for switch, value in switches.items():
-        monkeypatch.setattr(voice_bank, switch, value)
-    monkeypatch.setattr(config, "_sample_rate", 48000)
-    bank = voice_bank.try_build_bank(voices(pg, kind, count))
-    assert bank is not None and bank.k == count
-    if mix_windows:
-        bank.set_mix_windows()
-    for pull in {"LONG": LONG, "SHORT": SHORT}[pulls]:
-        if pull == "reset":
-            rec.note("reset")
-            bank.reset()
-            continue
-        rec.note("pull", *pull)
-        out = bank.render_mix(*pull)
-        rec.note("return", rec.name(out.dev.ptr), out.duration, out.channels, bool(out._bank_window))
-        del out
-    del bank
-    gc.collect()
-    rec.recording = False
-    return rec.entries + [["unreleased", label] for number, label in rec.names.items() if number in rec.alive]
-
-
-def launches(trace):
-    return [entry for entry in trace if entry[0] not in ("free", "unreleased")]
-
-
-def release_points(trace):
-    """buffer -> entries in front of its release (a buffer never released: more than there are)."""
-    points, seen = {}, 0
-    for entry in trace:
-        if entry[0] == "free":
-            points[entry[1]] = seen
-        elif entry[0] == "unreleased":
-            points[entry[1]] = len(trace) + 1
-        else:
-            seen += 1
-    return points
-
-
-@functools.lru_cache(None)
-def _recorded():
-    with open(FIXTURE) as f:
-        return {name: trace for name, trace in (json.loads(line) for line in f if line.strip())}
+    return run(monkeypatch, lambda: voices(pg, kind, count), {"LONG": LONG, "SHORT": SHORT}[pulls],
+               switches=switches, mix_windows=mix_windows)
 
 
 @pytest.mark.parametrize("name", list(CASES))
 def test_launch_trace(monkeypatch, name):
-    want = _recorded()[name]
-    got = json.loads(json.dumps(run_case(monkeypatch, name)))
+    got = run_case(monkeypatch, name)
     calls = {(entry[0], entry[1]) for entry in launches(got)}
     for expected in CASES[name][5]:
         assert tuple(expected) in calls, f"{name}: {expected[0]} on stream {expected[1]} does not occur"
-    a, b = launches(got), launches(want)
-    for i, (x, y) in enumerate(zip(a, b)):
-        assert x == y, f"{name}: entry {i} is {x}, recorded {y} (after {a[max(0, i - 3):i]})"
-    assert len(a) == len(b), f"{name}: {len(a)} entries, recorded {len(b)}"
-    now, then = release_points(got), release_points(want)
-    early = {buf: (now.get(buf), at) for buf, at in then.items() if buf not in now or now[buf] < at}
-    assert not early, f"{name}: released earlier than recorded (buffer: entries in front now, recorded): {early}"
-    late = {buf: (now[buf], at) for buf, at in then.items() if now[buf] > at}
-    if late:
-        warnings.warn(f"{name}: released later than recorded (buffer: entries in front now, recorded): {late}")
+    assert_matches(name, got, recorded(FIXTURE)[name])
 
 
 def test_fixture_has_every_case_once():
-    with open(FIXTURE) as f:
-        names = [json.loads(line)[0] for line in f if line.strip()]
-    assert names == list(CASES)
+    assert recorded_names(FIXTURE) == list(CASES)
 
 
 if __name__ == "__main__":
-    if sys.argv[1:] != ["--record"]:
-        sys.exit(__doc__)
-    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-    with open(FIXTURE, "w") as f:
-        for case in CASES:
-            patch = pytest.MonkeyPatch()
-            try:
-                trace = run_case(patch, case)
-            finally:
-                patch.undo()
-            f.write(json.dumps([case, trace], separators=(",", ":")) + "\n")
-            print(case, len(trace))
+    record_main(FIXTURE, CASES, run_case)
