@@ -167,6 +167,23 @@ int pgx_sine_stateful(float *out, int64_t n, int channels, double sample_rate,
                       const float *freq, const float *amp, const float *phase_mod,
                       double *state /* [2] */);
 
+/* A bank of stateful sines (voice_bank.py: FM / AM / PM voices).  Voice v writes n * channels float32 at out + v *
+ * out_stride, reads params[v] and its (n, 1) streams at freq + v * freq_stride, amp + v * amp_stride, phase_mod + v *
+ * phase_stride (NULL: the scalar of params[v], as above), and carries state[v] = { accumulated_phase, initialised flag }.
+ * workspace: pgx_sine_stateful_bank_workspace_bytes(n, batch) bytes, or NULL.  Without one, or for blocks of one or two
+ * tiles of 2 048 frames (or more than 2^22), one workgroup per voice walks its row in ONE launch; with one, a workgroup per
+ * tile and voice in two launches (the tiles' totals; their left fold in tile order and the frames).  Either way row v holds the float32
+ * samples and state[v] the final { phase, 1.0 } that pgx_sine_stateful(row v, params[v], voice v's streams, state[v]) gives,
+ * bit for bit.
+ * n <= 0 or batch <= 0: PGX_OK, nothing launched.  batch > 65535, channels < 1, sample_rate <= 0, a stride below its row,
+ * a null out / params / state: PGX_ERR_INVALID, nothing launched. */
+size_t pgx_sine_stateful_bank_workspace_bytes(int64_t n, int batch);
+int pgx_sine_stateful_bank(float *out, int64_t out_stride, int batch, int64_t n, int channels, double sample_rate,
+                           const pgx_sine_stateful_params *params /* device [batch] */,
+                           const float *freq, int64_t freq_stride, const float *amp, int64_t amp_stride,
+                           const float *phase_mod, int64_t phase_stride,
+                           double *state /* [batch][2] */, void *workspace /* or NULL */);
+
 /* ------------------------------------------------------------------ GainPE / MixPE
  * GainPE._render (gain_pe.py:92-127): one float32 multiply -> bit-exact.
  * MixPE._render (mix_pe.py:91-94): float32 adds in input order -> bit-exact. */

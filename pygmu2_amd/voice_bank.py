@@ -11,7 +11,8 @@ K voices in input order in float32 -- the same additions, in the same order, as 
 The batched kernels are the very same kernels the single PEs use (batch = 1 there), so a
 bank produces the same samples as rendering the voices one by one.
 
-Supported nodes: SinePE (scalar), FunctionGenPE (scalar), NoisePE, BlitSawPE (scalar), SuperSawPE (scalar),
+Supported nodes: SinePE (scalar, or frequency / amplitude / phase driven by single-channel PEs of batchable classes),
+FunctionGenPE (scalar), NoisePE, BlitSawPE (scalar), SuperSawPE (scalar),
 AnalogOscPE (scalar parameters, or
 single-channel PEs of batchable classes), BiquadPE (constant coefficients, or cutoff and / or Q driven by single-channel
 PEs of batchable classes), LadderPE (scalar controls), CombPE (scalar controls), GainPE (constant or PE gain), TransformPE
@@ -55,6 +56,16 @@ then ONE call runs pgx_biquad_varying's plan with the voice in the grid: each vo
 PE's, bit for bit.  From BIQUAD_VAR_WALK_MIN_ROWS rows (voices x channels) on the node passes no workspace: every row is
 walked by one workgroup in one launch, the same recurrence in another association (within a float32 rounding).  Banked
 from BIQUAD_VAR_MIN_VOICES voices on (both measured: tools/swept_bank_probe.py).
+
+Modulated-sine voices (pgx_sine_stateful_bank, _SineModNode): a SinePE whose frequency, amplitude or phase is a PE -- FM,
+tremolo, phase modulation -- is a kind of its own, key ("sine_mod", channels, freq_is_pe, amp_is_pe, phase_is_pe, ...); the
+scalars of the other parameters are per-voice data.  The modulators are batched levels rendered first (one that is itself
+a modulated sine has the same kind: nested FM), then ONE call runs the PE's kernel with the voice in the grid, {phase,
+initialised} carried per voice: samples and state are the PE's, bit for bit, on either plan -- a workgroup per tile and
+voice in two launches (the tiles' totals, then their left fold in tile order and the frames), or from
+SINE_MOD_WALK_MIN_ROWS voices on one workgroup per voice walking its row.  Like the PE the node carries the phase through a
+seek and clears it on start and stop; a phase in play (SinePE._look_ahead_condition) forbids windows.  Banked from
+SINE_MOD_MIN_VOICES voices on (both measured: tools/fm_bank_probe.py).
 
 AnalogOscPE voices (pgx_analog_osc_bank): the voice is a grid dimension of the PE's own scan kernels, so a bank of K
 takes the launches of one PE -- 1 (pure rectangle), 3 (pure sawtooth, stateful rectangle), 5 (stateful sawtooth) -- and
@@ -144,6 +155,22 @@ NOISE_MIN_VOICES = 64         # ... and for voices that hold a NoisePE (_NoiseNo
                               # recurrences side by side last as long as one), the hi-hat voice from 64 (16 voices, 1 024 frames: 61 / 50).
                               # The smallest K measured at which the bank is not slower at either block length in ANY mode, nor at a
                               # larger K (between 16 and 64: not measured).  One number for the three modes: a minimum per mode is open
+SINE_MOD_MIN_VOICES = 16      # ... and for voices that hold a SinePE with a PE parameter (_SineModNode): tools/fm_bank_probe.py, MixPE of K
+                              # SinePE(frequency=TransformPE(SinePE, Affine)), us per block bank / per voice, look-ahead on, streams of
+                              # 248 blocks of 1 024 frames and of 8 of 48 000 (profiles/fm_bank_probe.md; the spread of three passes
+                              # is below 1 us in the rows that decide) -- 1 024 frames: 4 voices 22 / 8.5, 8: 22 / 16.5, 16: 22 / 32,
+                              # 64: 22 / 131, 512: 26 / 1 054; 48 000: 31 / 367, 31 / 731, 31 / 1 457, 56 / 5 819, 235 / 46 523 (a voice
+                              # alone is one workgroup walking its block: 92 us).  The smallest K measured from which the bank wins
+                              # every row, and every row of a larger K (between 8 and 16: not measured).  The same voice under an
+                              # AdsrTriggeredPE envelope wins from 64 on (16 voices, 1 024 frames: 57 / 52) -- the minimum that class
+                              # already asks for
+SINE_MOD_WALK_MIN_ROWS = 512  # voices from which _SineModNode passes no workspace: one workgroup per voice walks the block in one
+                              # launch instead of the time-parallel form's two (blocks of up to two tiles of 2 048 frames are walked
+                              # either way).  The same probe, 48 000-frame blocks, us per block walk / time-parallel -- fm: 4 voices
+                              # 90 / 31, 16: 98 / 31, 64: 123 / 56, 256: 164 / 138, 512: 235 / 249; under the envelope: 111 / 79,
+                              # 115 / 89, 135 / 117, 209 / 207, 362 / 349 (within the spread).  The smallest K measured from which the
+                              # walk is not slower in any row (256 -- a workgroup per CU, the value before the probe -- loses the fm
+                              # row; between 256 and 512: not measured)
 BANK_WINDOWS = True           # a small bank streamed in equal blocks: 2, 4, 8 blocks per render, handed out as rows (VoiceBank)
 BANK_WINDOWS_ANY_ROOT = os.environ.get("PGX_BANK_WINDOWS_ANY_ROOT", "0") == "1"     # experiments (C5: measured slower)
 BANK_WINDOW_FIRST = 2
@@ -428,6 +455,56 @@ class _SineNode(_Node):
         out = DeviceBuffer((self.k, n, self.ch), np.float32)
         check(lib().pgx_sine_render(out.ptr, n * self.ch, self.k, start, n, self.ch, self.sr,
                                     self.params.ptr), "pgx_sine_render")
+        return out
+
+
+class _SineModNode(_Node):
+    """Bank of SinePEs with PE-valued parameters -- FM, AM, PM voices: pgx_sine_stateful_bank, the PE's kernel with the
+    voice in the grid.  The children's [K][n][1] streams first, then one call; the scalars of the other parameters are
+    per-voice data (`params`, the record SinePE._render fills), {accumulated phase, initialised} is carried per voice in
+    `state`, zeroed by reset() as SinePE._clear_phase does on start and stop.  Like the PE the node carries the phase
+    whatever `start` is.  Below SINE_MOD_WALK_MIN_ROWS voices the entry gets a workspace: a workgroup per tile and
+    voice, two launches; from there on a workgroup per voice walks its row.  Each voice's samples and state are the
+    PE's either way, bit for bit.  A phase in play (a PE, or a scalar that is not 0) makes the carried phase depend on
+    where the blocks are cut (SinePE._look_ahead_condition): no windows then."""
+
+    _STATE = ("state",)
+    _STREAMS = ("frequency", "amplitude", "phase")
+    TILE = 2048                  # frames per tile of the entry (pgx_scan.hip: kSinTile)
+
+    @classmethod
+    def scratch_bytes(cls, n: int, k: int) -> int:
+        """What the time-parallel form needs (pygmu_hip.h): per voice {phase, initialised} as they were on entry and one
+        total per tile, float64.  The library exports the same number; the node restates it because the guard-band
+        sweep (tests/test_gpu_guard_bands.py) counts the sizing exports this package calls against its own guarded runs,
+        and this node's guarded runs are tests/test_gpu_fm_voices.py's.  tests/test_fm_bank_host.py holds the two equal."""
+        return k * (-(-n // cls.TILE) + 2) * 8
+
+    def __init__(self, pes, children):
+        super().__init__(pes, children)
+        self.params = _dev.upload_structs(_param_records(_dev.SINE_STATEFUL_PARAMS, pes, lambda pe: dict(
+            freq=0.0 if _is_pe(pe._frequency) else float(pe._frequency),
+            amp=0.0 if _is_pe(pe._amplitude) else float(pe._amplitude),
+            phase=0.0 if _is_pe(pe._phase) else float(pe._phase), phase_is_stream=int(_is_pe(pe._phase)))))
+        self.ch = pes[0]._channels
+        self.state = DeviceBuffer((self.k, 2), np.float64, zero=True)
+        self._REQUEST_DEPENDENT = any(_is_pe(pe._phase) or float(pe._phase) != 0.0 for pe in pes)
+
+    def reset(self):
+        super().reset()
+        self.state.zero_()
+
+    def channels(self):
+        return self.ch
+
+    def render(self, start, n):
+        L = lib()
+        streams = [self.children[name].render(start, n) if name in self.children else None for name in self._STREAMS]
+        ws = None if self.k >= SINE_MOD_WALK_MIN_ROWS else self._scratch_of(self.scratch_bytes(n, self.k))
+        out = DeviceBuffer((self.k, n, self.ch), np.float32)
+        check(L.pgx_sine_stateful_bank(out.ptr, n * self.ch, self.k, n, self.ch, self.sr, self.params.ptr,
+                                       *_rows(streams[0], n), *_rows(streams[1], n), *_rows(streams[2], n),
+                                       self.state.ptr, ptr(ws)), "pgx_sine_stateful_bank")
         return out
 
 
@@ -1746,7 +1823,16 @@ def _transform_codes(pe):
 
 
 _KINDS = (
-    _Kind(SinePE, "sine", lambda pe: not pe._has_pe_inputs(), lambda pe: (pe._channels,), (), _SineNode),
+    # (all scalars: _SineNode, key ("sine", channels); a PE-driven frequency, amplitude or phase -- FM, AM, PM: _SineModNode --
+    # the scalars of the other parameters are per-voice data there, which parameters are PEs is part of the key)
+    _Kind(SinePE, lambda pe: "sine_mod" if pe._has_pe_inputs() else "sine", _osc_batchable,
+          lambda pe: ((pe._channels, _is_pe(pe._frequency), _is_pe(pe._amplitude), _is_pe(pe._phase))
+                      if pe._has_pe_inputs() else (pe._channels,)),
+          (("frequency", "_frequency", lambda pe: _is_pe(pe._frequency)),
+           ("amplitude", "_amplitude", lambda pe: _is_pe(pe._amplitude)),
+           ("phase", "_phase", lambda pe: _is_pe(pe._phase))),
+          lambda pes, children: _SineModNode(pes, children) if children else _SineNode(pes),
+          lambda pe: SINE_MOD_MIN_VOICES if pe._has_pe_inputs() else MIN_VOICES),
     # (a FunctionGenPE with a PE parameter carries a phase and restarts on a seek: not batched -- PeriodicGate's rule)
     _Kind(FunctionGenPE, "function_gen", lambda pe: pe.is_pure(), lambda pe: (pe._waveform, pe._channels), (),
           _FunctionGenNode),
