@@ -401,7 +401,8 @@ int pgx_interp_lookup(float *out, const float *window, int64_t window_start, int
                       int channels, int64_t start, int64_t n, double delay_scalar, const float *delay,
                       int cubic, int bounded, double extent_start, double extent_end);
 /* result_dev[0..1] = min, max of float64(start + i) - delay[i]  (np.min / np.max of the indices,
- * interpolated_lookup.py:111-112): the host sizes the source window from them. */
+ * interpolated_lookup.py:111-112): the host sizes the source window from them.  A NaN anywhere in the stream gives
+ * (NaN, NaN). */
 int pgx_index_range(double *result_dev, const float *delay, int64_t start, int64_t n);
 /* ------------------------------------------------------------------ WavetablePE / TimeWarpPE
  * The two other callers of interpolated_lookup, through the same device function as pgx_interp_lookup.
@@ -418,13 +419,21 @@ int pgx_index_range(double *result_dev, const float *delay, int64_t start, int64
 int pgx_wavetable(float *out, const float *indexer, int64_t n, const float *window, int64_t window_start,
                   int64_t window_len, int channels, int cubic, int oob_mode, int finite, double wt_start,
                   double wt_end);
+/* out[0] = 1 if pgx_wavetable would stage the window in LDS for these arguments (PGX_WT_LDS_FLOATS included), out[1] = its
+ * grid.  The window is staged when window_len * channels is at most 2560 floats (PGX_WT_LDS_FLOATS: another limit, at
+ * most 16384; 0: never) and the n frames make at least as many gathers as that (2 per channel linear, 4 cubic).  Host
+ * arithmetic only: needs no device and no pgx_init.  n <= 0: PGX_OK and out = {0, 0}, as pgx_wavetable launches nothing.
+ * out is host memory, handed over as a plain address (a ctypes array of two ints, or NULL). */
+int pgx_wavetable_plan(int64_t n, int64_t window_len, int channels, int cubic, int out[2]);
 /* result_dev[0..1] = min, max of those processed indices (np.min / np.max, interpolated_lookup.py:126-127) for a
- * table whose window is not kept on the device: the host sizes the table render from them. */
+ * table whose window is not kept on the device: the host sizes the table render from them.  A NaN anywhere in the
+ * stream gives (NaN, NaN). */
 int pgx_wavetable_range(double *result_dev, const float *indexer, int64_t n, int oob_mode, int finite,
                         double wt_start, double wt_end);
 /* TimeWarpPE._render with a PE rate, index side (timewarp_pe.py:150-163): positions[i] = state[0] +
  * sum(rate[0..i)) (np.cumsum; here a float64 scan over workgroup segments), range_dev[0..1] = min, max of the
- * positions, then state[0] += sum(rate).  workspace: PGX_TIMEWARP_WORKSPACE_DOUBLES doubles of scratch. */
+ * positions ((NaN, NaN) if any position is NaN), then state[0] += sum(rate).  workspace:
+ * PGX_TIMEWARP_WORKSPACE_DOUBLES doubles of scratch. */
 #define PGX_TIMEWARP_WORKSPACE_DOUBLES 768
 int pgx_timewarp_scan(double *positions, double *range_dev, double *state, double *workspace, const float *rate,
                       int64_t n);
@@ -435,7 +444,8 @@ int pgx_timewarp(float *out, int64_t n, const double *positions, double pos0, do
                  int64_t window_start, int64_t window_len, int channels, int cubic, int has_start,
                  double extent_start, int has_end, double extent_end);
 /* partials_dev[2 p + {0, 1}] = (min, max) of workgroup p's share of the mono stream x[0..n), p < parts <= 1024
- * (NaN if it met one): the host folds the pairs.  LadderPE with a PE-driven cutoff / resonance sizes the warm-up
+ * ((NaN, NaN) if it met a NaN anywhere in its share; (+inf, -inf) if its share is empty): the host folds the pairs,
+ * so a NaN anywhere in the stream gives (NaN, NaN).  LadderPE with a PE-driven cutoff / resonance sizes the warm-up
  * of its time segments from the block's lowest cutoff and highest resonance (ladder_pe.py:84-113 clamps). */
 int pgx_stream_range(double *partials_dev, int parts, const float *x, int64_t n);
 /* PiecewisePE._render (piecewise_pe.py:164-229); times sorted int64, values float64 (device).

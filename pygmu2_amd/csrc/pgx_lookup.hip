@@ -68,17 +68,24 @@ k_interp_lookup(float *out, const float *win, int64_t win_start, int64_t win_len
     }
 }
 
-// min / max of float64(start + i) - delay[i] over the block -> result[0..1]  (one workgroup)
+// One element into a thread's running (min, max) of a range reduction.  np.min / np.max propagate NaN, fmin / fmax drop
+// it as soon as a number follows: `nan` is the thread's sticky flag, folded in (lo = hi = NaN) before the workgroup's
+// reduction, which keeps a NaN from then on.
+__device__ __forceinline__ void range_take(double &lo, double &hi, bool &nan, double v) {
+    lo = fmin(lo, v);
+    hi = fmax(hi, v);
+    nan = nan || v != v;
+}
+
+// min / max of float64(start + i) - delay[i] over the block -> result[0..1]  (one workgroup); (NaN, NaN) if any index
+// is NaN: the host rejects such a delay stream
 __global__ void __launch_bounds__(kBlock)
 k_index_range(double *result, const float *delay, int64_t start, int64_t n) {
     __shared__ double smin[kBlock], smax[kBlock];
     double lo = INFINITY, hi = -INFINITY;
-    for (int64_t i = threadIdx.x; i < n; i += kBlock) {
-        const double index = (double)(start + i) - (double)delay[i];
-        lo = fmin(lo, index);            // np.min / np.max propagate NaN; a NaN delay is rejected on the host
-        hi = fmax(hi, index);
-        if (index != index) lo = hi = index;
-    }
+    bool nan = false;
+    for (int64_t i = threadIdx.x; i < n; i += kBlock) range_take(lo, hi, nan, (double)(start + i) - (double)delay[i]);
+    if (nan) lo = hi = NAN;
     smin[threadIdx.x] = lo;
     smax[threadIdx.x] = hi;
     __syncthreads();
@@ -104,10 +111,7 @@ k_stream_range(double *partials, const float *x, int64_t n) {
     double lo = INFINITY, hi = -INFINITY;
     bool nan = false;
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
-        const double v = (double)x[i];
-        lo = fmin(lo, v);
-        hi = fmax(hi, v);
-        nan = nan || v != v;
+        range_take(lo, hi, nan, (double)x[i]);
     }
     if (nan) lo = hi = NAN;
     smin[threadIdx.x] = lo;
@@ -199,19 +203,19 @@ __device__ __forceinline__ void block_range(double &lo, double &hi, double *smin
     __syncthreads();
 }
 
-// min / max of the processed indices -> result[0..1] (one workgroup): the window of a table that is not kept
+// min / max of the processed indices -> result[0..1] (one workgroup): the window of a table that is not kept;
+// (NaN, NaN) if any processed index is NaN
 __global__ void __launch_bounds__(kBlock)
 k_wavetable_range(double *result, const float *indexer, int64_t n, int mode, int finite, double wt_start,
                   double wt_end) {
     __shared__ double smin[kBlock], smax[kBlock];
     double lo = INFINITY, hi = -INFINITY;
+    bool nan = false;
     for (int64_t i = threadIdx.x; i < n; i += kBlock) {
         bool oob;
-        const double index = wt_index((double)indexer[i], mode, finite, wt_start, wt_end, oob);
-        lo = fmin(lo, index);
-        hi = fmax(hi, index);
-        if (index != index) lo = hi = index;
+        range_take(lo, hi, nan, wt_index((double)indexer[i], mode, finite, wt_start, wt_end, oob));
     }
+    if (nan) lo = hi = NAN;
     block_range(lo, hi, smin, smax);
     if (threadIdx.x == 0) {
         result[0] = lo;
@@ -260,6 +264,7 @@ k_tw_positions(double *positions, double *segrange, double *range, double *state
     const int64_t first = (int64_t)blockIdx.x * seg_frames;
     const int64_t end = first + seg_frames < n ? first + seg_frames : n;
     double lo = INFINITY, hi = -INFINITY;
+    bool nan = false;
     for (int64_t base = first; base < end; base += kTwTile) {
         const int64_t f0 = base + (int64_t)threadIdx.x * kTwT;
         double before[kTwT];
@@ -277,12 +282,11 @@ k_tw_positions(double *positions, double *segrange, double *range, double *state
             if (f0 + j < end) {
                 const double p = pos + (off + before[j]);
                 positions[f0 + j] = p;
-                lo = fmin(lo, p);
-                hi = fmax(hi, p);
-                if (p != p) lo = hi = p;
+                range_take(lo, hi, nan, p);
             }
         }
     }
+    if (nan) lo = hi = NAN;
     block_range(lo, hi, smin, smax);
     if (threadIdx.x == 0) {
         if (gridDim.x == 1) {
@@ -593,6 +597,31 @@ k_mono_mean(float *out, const float *in, int64_t n, int src_ch) {
         out[i] = row_mean(in + i * src_ch, 0, src_ch);
 }
 
+// How pgx_wavetable launches k_wavetable (also what pgx_wavetable_plan answers): the window is staged when it fits the
+// limit and the launch has at least as many gathers to make as floats to stage.
+struct WtPlan {
+    int staged;
+    int grid;
+};
+
+WtPlan wavetable_plan(int64_t n, int64_t window_len, int channels, int cubic) {
+    const int64_t floats = window_len * channels;
+    const int taps = cubic ? 4 : 2;
+    WtPlan p{0, pgx::grid_for(n, kBlock)};
+    // PGX_WT_LDS_FLOATS (experiments, tools/playback_probe.py): another staging limit; 0 gathers from global memory
+    const char *lds_env = getenv("PGX_WT_LDS_FLOATS");
+    int64_t lds_floats = lds_env ? atoi(lds_env) : kWtLdsFloats;
+    if (lds_floats > kWtLdsMaxFloats) lds_floats = kWtLdsMaxFloats;
+    if (floats <= lds_floats && n * taps * channels >= floats) {
+        // a workgroup stages the whole window: give each one at least as many gathers as that costs
+        p.staged = 1;
+        const int64_t per_group = pgx::ceil_div(floats, (int64_t)taps * channels);
+        const int64_t groups = n / (per_group > kBlock ? per_group : kBlock);
+        if (groups < p.grid) p.grid = groups < 1 ? 1 : (int)groups;
+    }
+    return p;
+}
+
 }  // namespace
 
 extern "C" {
@@ -704,25 +733,24 @@ int pgx_wavetable(float *out, const float *indexer, int64_t n, const float *wind
     if (n <= 0) return PGX_OK;
     PGX_CHECK_ARG(out && indexer && window && window_len >= 1 && channels >= 1 && oob_mode >= 0 && oob_mode <= 2,
                   "pgx_wavetable: bad argument");
-    const int64_t floats = window_len * channels;
-    const int taps = cubic ? 4 : 2;
-    int grid = pgx::grid_for(n, kBlock);
-    int staged = 0;
-    // PGX_WT_LDS_FLOATS (experiments, tools/playback_probe.py): another staging limit; 0 gathers from global memory
-    const char *lds_env = getenv("PGX_WT_LDS_FLOATS");
-    int64_t lds_floats = lds_env ? atoi(lds_env) : kWtLdsFloats;
-    if (lds_floats > kWtLdsMaxFloats) lds_floats = kWtLdsMaxFloats;
-    if (floats <= lds_floats && n * taps * channels >= floats) {
-        // a workgroup stages the whole window: give each one at least as many gathers as that costs
-        staged = 1;
-        const int64_t per_group = pgx::ceil_div(floats, (int64_t)taps * channels);
-        const int64_t groups = n / (per_group > kBlock ? per_group : kBlock);
-        if (groups < grid) grid = groups < 1 ? 1 : (int)groups;
-    }
-    hipLaunchKernelGGL(k_wavetable, dim3(grid), dim3(kBlock), staged ? (size_t)floats * sizeof(float) : 0,
-                       pgx::stream(), out, indexer, n, window, window_start, window_len, channels, cubic ? 1 : 0,
-                       oob_mode, finite ? 1 : 0, wt_start, wt_end, staged);
+    const WtPlan plan = wavetable_plan(n, window_len, channels, cubic);
+    const size_t lds_bytes = plan.staged ? (size_t)(window_len * channels) * sizeof(float) : 0;
+    hipLaunchKernelGGL(k_wavetable, dim3(plan.grid), dim3(kBlock), lds_bytes, pgx::stream(), out, indexer, n, window,
+                       window_start, window_len, channels, cubic ? 1 : 0, oob_mode, finite ? 1 : 0, wt_start, wt_end,
+                       plan.staged);
     PGX_LAUNCH_CHECK("k_wavetable");
+    return PGX_OK;
+}
+
+int pgx_wavetable_plan(int64_t n, int64_t window_len, int channels, int cubic, int out[2]) {
+    if (n <= 0) {                                            // pgx_wavetable launches nothing
+        if (out) out[0] = out[1] = 0;
+        return PGX_OK;
+    }
+    PGX_CHECK_ARG(out && window_len >= 1 && channels >= 1, "pgx_wavetable_plan: bad argument");
+    const WtPlan plan = wavetable_plan(n, window_len, channels, cubic);
+    out[0] = plan.staged;
+    out[1] = plan.grid;
     return PGX_OK;
 }
 

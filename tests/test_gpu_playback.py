@@ -160,6 +160,13 @@ def test_non_finite_positions_raise():
         pg.TimeWarpPE(pg.SinePE(220.0), float("nan")).render(0, 64)
     with pytest.raises(ValueError, match="non-finite"):
         pg.WavetablePE(pg.SinePE(100.0), pg.ConstantPE(float("nan"))).render(0, 64)
+    # one NaN at frame 0 of a block longer than the range kernels' thread stride: frames 256 and 512 follow it
+    stream = np.linspace(1.0, 40.0, 600, dtype=np.float32)
+    stream[0] = np.nan
+    with pytest.raises(ValueError, match="non-finite"):
+        pg.DelayPE(pg.SinePE(220.0), delay=pg.ArrayPE(stream)).render(0, 600)
+    with pytest.raises(ValueError, match="non-finite"):
+        pg.WavetablePE(pg.SinePE(100.0), pg.ArrayPE(stream)).render(0, 600)
 
 
 # ---------------------------------------------------------------------------------------------- example 20
