@@ -259,6 +259,27 @@ int pgx_biquad_sine_set_pacing(int mode);
  * host memory. */
 int pgx_biquad_sine_pacing_info(int64_t out[3]);
 
+/* The same chain over window-sized blocks in closed form (pgx_tone.hip): once the filter's transient has died the
+ * output of a constant section driven by a pure tone is that tone scaled by |H(e^jw/sr)| and shifted by arg H, so
+ * out[i] = float32(amp |H| sin(phase0 + arg H + w (start + i) / sr)) with no recurrence, no warm-up and no state
+ * carried from lane to lane.  What the closed form leaves out is the filter's answer to the float32 rounding of the
+ * input samples, at most 2^-25 sum|h| / |H| of the output's peak.
+ * pgx_biquad_tone_supported: 1 when settle_frames > 0, n >= 2 settle_frames, |w| n / sr stays in the fast sine's
+ * range and sum|h| / |H| <= 4 (h: the first settle_frames samples of the impulse response; H in long double) -- the
+ * omitted rounding noise then stays below 1.2e-7 of the peak.  A host computation: no device is needed.
+ * pgx_biquad_tone_gain / pgx_biquad_tone_l1: the |H| and the sum|h| that test uses.
+ * pgx_biquad_tone: coefficients by value; tables, state and state_backup as for pgx_biquad_sine.  The carried state
+ * enters as the zero-input response of (state - the steady solution's state at start - 1) over the first
+ * settle_frames frames; state_backup (or NULL) receives the incoming state bit for bit; state leaves as the steady
+ * solution's DF-II-T state at the last frame (x taken as the float32-rounded tone). */
+int pgx_biquad_tone_supported(int64_t n, int64_t settle_frames, double w, double sample_rate, double b0, double b1,
+                              double b2, double a1, double a2);
+double pgx_biquad_tone_gain(double w, double sample_rate, double b0, double b1, double b2, double a1, double a2);
+double pgx_biquad_tone_l1(int64_t settle_frames, double b0, double b1, double b2, double a1, double a2);
+int pgx_biquad_tone(float *out, int64_t start, int64_t n, double sample_rate, double w, double amp, double phase0,
+                    double b0, double b1, double b2, double a1, double a2, const double *tables,
+                    int64_t settle_frames, double *state /* [2] */, double *state_backup /* [2] or NULL */);
+
 /* Time-varying coefficients: _compute_coefficients per sample (biquad_pe.py:217-335) +
  * the direct-form-I recurrence of _biquad_varying_numba (biquad_pe.py:35-62).
  * freq/q: per-sample float32 control streams (frames,1) or NULL -> scalar.

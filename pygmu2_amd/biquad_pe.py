@@ -13,7 +13,9 @@ from __future__ import annotations
 
 from enum import Enum
 
+import ctypes
 import math
+import os
 
 import numpy as np
 
@@ -28,6 +30,9 @@ from .snippet import Snippet
 
 FUSE_SINE_SOURCE = True        # BiquadPE(SinePE): generate the sine inside the filter kernel (pgx_biquad_sine)
 SINE_FAST_RANGE = 2.0e9        # pgx_common.h kSinFastRange: beyond it the two PEs render separately
+# window-sized renders of that chain in closed form (pgx_biquad_tone) where the filter passes the tone well above the
+# float32 rounding noise of its input (pgx_biquad_tone_supported); PYGMU_BIQUAD_TONE=0 keeps the wave-run kernel
+TONE_WINDOWS = os.environ.get("PYGMU_BIQUAD_TONE", "1") != "0"
 
 
 class BiquadMode(Enum):
@@ -178,6 +183,7 @@ class BiquadPE(ProcessingElement):
         self._coef_host = None
         self._sine_chain_memo = None                  # _sine_chain(), evaluated once
         self._sine_supported: dict = {}               # duration -> pgx_biquad_sine_supported
+        self._tone_supported: dict = {}               # duration -> window-sized and pgx_biquad_tone_supported
         self._backup_target = None                    # a snapshot buffer the next fused render has to fill
         self._backup_ring = []                        # three small buffers used in turn as snapshot targets
         self._backup_turn = 0
@@ -276,9 +282,27 @@ class BiquadPE(ProcessingElement):
         self._ensure_state(1)
         out = new_output(duration, 1)
         backup, self._backup_target = self._backup_target, None      # a look-ahead window's snapshot: the kernel fills it
+        if self._takes_tone_window(L, start, duration, w, phase, sr):
+            check(L.pgx_biquad_tone(out.ptr, start, duration, sr, w, amp, phase, *self._coef_host, self._tables.ptr,
+                                    self._settle, self._state.ptr, ptr(backup)), "pgx_biquad_tone")
+            return Snippet(start, out)
         check(L.pgx_biquad_sine(out.ptr, start, duration, sr, w, amp, phase, self._coef.ptr, self._tables.ptr,
                                 self._settle, self._state.ptr, ptr(backup)), "pgx_biquad_sine")
         return Snippet(start, out)
+
+    def _takes_tone_window(self, L, start: int, duration: int, w: float, phase: float, sr: float) -> bool:
+        """Window-sized renders (the sizes pgx_biquad_sine would hand to its wave-run kernel, 16 M frames and up) of a chain
+        pgx_biquad_tone_supported accepts are rendered in closed form; everything else goes on as before."""
+        if not TONE_WINDOWS:
+            return False
+        ok = self._tone_supported.get(duration)
+        if ok is None:
+            plan = (ctypes.c_int * 5)()
+            ok = self._tone_supported[duration] = bool(
+                L.pgx_biquad_sine_runs_plan(duration, self._settle, plan)
+                and L.pgx_biquad_tone_supported(duration, self._settle, w, sr, *self._coef_host))
+        # (the frame before the block and the filter's phase shift stay inside the fast sine's range too)
+        return ok and abs(phase) + abs(w) * ((abs(start) + duration + 1) / sr) + 8.0 < SINE_FAST_RANGE
 
     def _la_take_snapshot(self):
         """look_ahead.take_snapshot: the state copy of a window over the fused sine chain is written by the window's

@@ -23,6 +23,7 @@ SOURCES = [
     "pgx_runtime.hip",
     "pgx_elementwise.hip",
     "pgx_scan.hip",
+    "pgx_tone.hip",
     "pgx_seq.hip",
     "pgx_comb.hip",
     "pgx_adsr.hip",

@@ -4,6 +4,7 @@
 //   hipcc --offload-arch=gfx950 -O3 -o tools/microbench/fill_rate tools/microbench/fill_rate.hip
 #include <hip/hip_runtime.h>
 #include <cstdio>
+#include <string>
 typedef float v4f __attribute__((ext_vector_type(4)));
 
 // A: grid-stride loop, one 16-byte store per thread and trip (the library's k_fill)
@@ -37,6 +38,18 @@ __global__ void __launch_bounds__(256) fill_c(float *out, long n4, float v, int 
         }
     }
 }
+// D: the closed-form window's shape (csrc/pgx_tone.hip): B's 16 KB piece per workgroup, four frames per lane and store,
+// written through (sc1) a buffer resource based at the piece, the values different in every lane
+typedef unsigned int v4u __attribute__((ext_vector_type(4)));
+__global__ void __launch_bounds__(256, 8) fill_d(float *out, long n, float v) {
+    const long p0 = (long)blockIdx.x * 4096;
+    const long left = n - p0;
+    __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(out + p0, 0, (int)(left < 4096 ? left : 4096) * 4, 0x00020000);
+    const unsigned a = __float_as_uint(v + (float)threadIdx.x);
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+        __builtin_amdgcn_raw_buffer_store_b128(v4u{a, a + 1, a + 2, a + 3}, rsrc, (threadIdx.x * 4 + u * 1024) * 4, 0, 16 /* sc1 */);
+}
 
 template <typename F>
 static void timeit(const char *name, long bytes, F launch) {
@@ -57,6 +70,9 @@ int main() {
     float *out;
     (void)hipMalloc(&out, bytes);
     timeit("hipMemsetAsync", bytes, [&] { (void)hipMemsetAsync(out, 0, bytes, 0); });
+    // (the 6.5 TB/s ceiling had only been taken with zeros: the same fill with a value that is not zero)
+    timeit("hipMemsetD32Async, 0x3e800000 (0.25f)", bytes, [&] { (void)hipMemsetD32Async((hipDeviceptr_t)out, 0x3e800000, n, 0); });
+    timeit("hipMemsetD32Async, 0", bytes, [&] { (void)hipMemsetD32Async((hipDeviceptr_t)out, 0, n, 0); });
     for (int wgs : {2048, 4096, 8192, 16384})
         timeit((std::string("A grid-stride, 16 B per trip, ") + std::to_string(wgs) + " workgroups").c_str(), bytes,
                [&] { hipLaunchKernelGGL(fill_a, dim3(wgs), dim3(256), 0, 0, out, n4, 0.25f); });
@@ -71,5 +87,8 @@ int main() {
     for (int tpw : {1, 8, 43})
         timeit((std::string("C filter-kernel layout (wave-contiguous 4 KB), ") + std::to_string(tpw) + " tiles per workgroup").c_str(), bytes,
                [&] { hipLaunchKernelGGL(fill_c, dim3((unsigned)((n / 4096 + tpw - 1) / tpw)), dim3(256), 0, 0, out, n4, 0.25f, tpw); });
+    timeit("D closed-form window's shape: 16 KB per workgroup, 4 frames per lane, write-through", bytes,
+           [&] { hipLaunchKernelGGL(fill_d, dim3((unsigned)((n + 4095) / 4096)), dim3(256), 0, 0, out, n, 0.25f); });
+    timeit("hipMemsetAsync (again, last)", bytes, [&] { (void)hipMemsetAsync(out, 0, bytes, 0); });
     return 0;
 }
