@@ -279,6 +279,22 @@ double pgx_biquad_tone_l1(int64_t settle_frames, double b0, double b1, double b2
 int pgx_biquad_tone(float *out, int64_t start, int64_t n, double sample_rate, double w, double amp, double phase0,
                     double b0, double b1, double b2, double a1, double a2, const double *tables,
                     int64_t settle_frames, double *state /* [2] */, double *state_backup /* [2] or NULL */);
+/* The window kernel is bound by its stores, so the size of a stream's windows is its business: the frames per look-ahead
+ * window at which the two live float32 mono windows of a stream (the one being served and the one just opened, whose
+ * buffers alternate) are still stored at the memory-side cache's rate, not HBM's, and the host's cost of opening a
+ * window is spread over as many frames as that allows.  0: no preference.
+ * PGX_TONE_WINDOW_FRAMES replaces the built-in figure (read once).  A host computation: no device is needed. */
+int64_t pgx_biquad_tone_window_frames(void);
+/* A stream opens a window every few microseconds of host time: pgx_biquad_tone_plan evaluates once what
+ * pgx_biquad_tone evaluates per call from its twelve chain constants (the gate, |H|, arg H, the rotation constants) and
+ * returns a handle (NULL: pgx_biquad_tone_supported declines the chain at every block length), which the caller frees
+ * with pgx_biquad_tone_plan_free; tables must outlive it.  pgx_biquad_tone_window(plan, ...) is pgx_biquad_tone with
+ * those constants: the same launch, the same bits in out, state and state_backup. */
+void *pgx_biquad_tone_plan(double sample_rate, double w, double amp, double phase0, double b0, double b1, double b2,
+                           double a1, double a2, const double *tables, int64_t settle_frames);
+int pgx_biquad_tone_plan_free(void *plan);
+int pgx_biquad_tone_window(const void *plan, float *out, int64_t start, int64_t n, double *state /* [2] */,
+                           double *state_backup /* [2] or NULL */);
 
 /* Time-varying coefficients: _compute_coefficients per sample (biquad_pe.py:217-335) +
  * the direct-form-I recurrence of _biquad_varying_numba (biquad_pe.py:35-62).

@@ -35,6 +35,28 @@ SINE_FAST_RANGE = 2.0e9        # pgx_common.h kSinFastRange: beyond it the two P
 TONE_WINDOWS = os.environ.get("PYGMU_BIQUAD_TONE", "1") != "0"
 
 
+def tone_window_frames() -> int:
+    """Frames per look-ahead window the closed-form window kernel asks for (pgx_biquad_tone_window_frames: two live
+    windows stay in the memory-side cache); 0: no preference."""
+    return int(_dev.load_library().pgx_biquad_tone_window_frames())
+
+
+class _TonePlan:
+    """Owner of a pgx_biquad_tone_plan handle."""
+    __slots__ = ("handle",)
+
+    def __init__(self, handle):
+        self.handle = handle
+
+    def __del__(self):
+        handle, self.handle = self.handle, None
+        if handle:
+            try:
+                _dev.load_library().pgx_biquad_tone_plan_free(handle)
+            except Exception:                         # noqa: BLE001 -- interpreter shutdown: the process frees it
+                pass
+
+
 class BiquadMode(Enum):
     LOWPASS = "lowpass"
     HIGHPASS = "highpass"
@@ -184,6 +206,8 @@ class BiquadPE(ProcessingElement):
         self._sine_chain_memo = None                  # _sine_chain(), evaluated once
         self._sine_supported: dict = {}               # duration -> pgx_biquad_sine_supported
         self._tone_supported: dict = {}               # duration -> window-sized and pgx_biquad_tone_supported
+        self._tone_plan: _TonePlan | None = None      # pgx_biquad_tone_plan of the chain, made at its first window
+        self._tone_hint = None                        # _look_ahead_frames(), evaluated once: (frames or None,)
         self._backup_target = None                    # a snapshot buffer the next fused render has to fill
         self._backup_ring = []                        # three small buffers used in turn as snapshot targets
         self._backup_turn = 0
@@ -283,8 +307,12 @@ class BiquadPE(ProcessingElement):
         out = new_output(duration, 1)
         backup, self._backup_target = self._backup_target, None      # a look-ahead window's snapshot: the kernel fills it
         if self._takes_tone_window(L, start, duration, w, phase, sr):
-            check(L.pgx_biquad_tone(out.ptr, start, duration, sr, w, amp, phase, *self._coef_host, self._tables.ptr,
-                                    self._settle, self._state.ptr, ptr(backup)), "pgx_biquad_tone")
+            plan = self._tone_plan
+            if plan is None:                          # the chain's constants, evaluated once: six arguments per window
+                plan = self._tone_plan = _TonePlan(L.pgx_biquad_tone_plan(sr, w, amp, phase, *self._coef_host,
+                                                                          self._tables.ptr, self._settle))
+            check(L.pgx_biquad_tone_window(plan.handle, out.ptr, start, duration, self._state.ptr, ptr(backup)),
+                  "pgx_biquad_tone_window")
             return Snippet(start, out)
         check(L.pgx_biquad_sine(out.ptr, start, duration, sr, w, amp, phase, self._coef.ptr, self._tables.ptr,
                                 self._settle, self._state.ptr, ptr(backup)), "pgx_biquad_sine")
@@ -303,6 +331,23 @@ class BiquadPE(ProcessingElement):
                 and L.pgx_biquad_tone_supported(duration, self._settle, w, sr, *self._coef_host))
         # (the frame before the block and the filter's phase shift stay inside the fast sine's range too)
         return ok and abs(phase) + abs(w) * ((abs(start) + duration + 1) / sr) + 8.0 < SINE_FAST_RANGE
+
+    def _look_ahead_frames(self):
+        """look_ahead.window_blocks: the frames per window the closed-form kernel asks for, when windows of that size
+        are rendered by it (the chain, the switches and pgx_biquad_tone_supported say so); None: no preference."""
+        if not (TONE_WINDOWS and FUSE_SINE_SOURCE) or _diag.is_enabled():
+            return None
+        if self._tone_hint is None:
+            frames, chain = tone_window_frames(), self._sine_chain()
+            ok = False
+            if frames > 0 and chain is not None:
+                L = lib()
+                plan = (ctypes.c_int * 5)()
+                ok = bool(L.pgx_biquad_sine_runs_plan(frames, self._settle, plan)
+                          and L.pgx_biquad_tone_supported(frames, self._settle, chain[0], float(self.sample_rate),
+                                                          *self._coef_host))
+            self._tone_hint = (frames if ok else None,)
+        return self._tone_hint[0]
 
     def _la_take_snapshot(self):
         """look_ahead.take_snapshot: the state copy of a window over the fused sine chain is written by the window's

@@ -27,10 +27,20 @@
 
 #include <cmath>
 
+// Switches of tools/c2_resident_probe.py (variants measured at cache-resident window sizes; the defaults are what
+// ships): the groups of four frames per thread (8: two 16 KB pieces per workgroup, which moves every second anchor) and
+// the cache policy of the full-group stores (16: sc1, write-through; 0: plain).
+#ifndef PGX_TONE_GROUPS
+#define PGX_TONE_GROUPS 4
+#endif
+#ifndef PGX_TONE_STORE_AUX
+#define PGX_TONE_STORE_AUX 16
+#endif
+
 namespace {
 
 constexpr int kToneBlock = 256;
-constexpr int kToneGroups = 4;                            // groups of four frames per thread
+constexpr int kToneGroups = PGX_TONE_GROUPS;              // groups of four frames per thread
 constexpr int kToneGroupStride = kToneBlock * 4;          // 1024 frames between a thread's groups
 constexpr int kTonePiece = kToneGroupStride * kToneGroups;   // 4096 frames = 16 KB per workgroup
 // the layout of pgx_biquad_tables (pgx_scan.hip k_biquad_tables): A^1024 at 24, A^(16 q) at 28 + 4 q (q < 64), the
@@ -127,7 +137,8 @@ __device__ __forceinline__ void tone_piece(float *__restrict__ out, int64_t n, c
             if (PGX_HOT(aligned && f + 4 <= n)) {
                 const tone_v4u v = {__float_as_uint((float)y[0]), __float_as_uint((float)y[1]),
                                     __float_as_uint((float)y[2]), __float_as_uint((float)y[3])};
-                __builtin_amdgcn_raw_buffer_store_b128(v, rsrc, (tid * 4 + u * kToneGroupStride) * 4, 0, 16 /* sc1 */);
+                __builtin_amdgcn_raw_buffer_store_b128(v, rsrc, (tid * 4 + u * kToneGroupStride) * 4, 0,
+                                                       PGX_TONE_STORE_AUX /* sc1 */);
             } else {
 #pragma unroll
                 for (int j = 0; j < 4; ++j)
@@ -233,36 +244,39 @@ static bool tone_supported(int64_t n, int64_t settle, double w, double sr, doubl
     return std::isfinite(f.gain) && std::isfinite(f.l1) && f.l1 <= kToneNoiseRatio * f.gain;
 }
 
-}  // namespace
+// Frames per look-ahead window of a stream of these windows.  The kernel is bound by its stores, and a stream has two
+// windows live (their buffers alternate): while both stay in the 256 MiB memory-side cache a window is overwritten with
+// its lines still on the die and is stored at the cache's rate (0.53 us per M frames + 1.8 us) instead of HBM's (0.67).
+// The sweep of profiles/c2_resident_windows.md, bench.py at 1 M-frame steps, Msamples/s of the parent's 1 449 000 -
+// 1 521 000 (134 M-frame windows): 24 M 1 309 000 - 1 323 000, 30 M 1 470 000 - 1 537 000, 32 M 1 497 000 - 1 586 000 (one
+// run 1 337 000), 34 M 1 570 000 - 1 629 000 (one 1 491 000), 36 M 1 585 000 - 1 679 000, 38 M 1 573 000 - 1 656 000, 40 M
+// 1 572 000 - 1 641 000, 44 M 1 541 000 - 1 654 000, 48 M 1 381 000 - 1 479 000.  Below 36 M the host bounds the stream (an
+// opening costs it 11 - 12 us, a served step 0.28), at 36 M the traced kernel still runs at the cache's rate (21.2 us,
+// 0.59 us per M frames) and host and device are level; from 40 M on the device falls back towards HBM's rate.
+constexpr int64_t kToneWindowFrames = 36000000;
 
-extern "C" {
-
-int pgx_biquad_tone_supported(int64_t n, int64_t settle_frames, double w, double sample_rate, double b0, double b1,
-                              double b2, double a1, double a2) {
-    return tone_supported(n, settle_frames, w, sample_rate, b0, b1, b2, a1, a2) ? 1 : 0;
+static int64_t tone_window_frames_env() {
+    const char *e = getenv("PGX_TONE_WINDOW_FRAMES");      // 0: no preference
+    if (e && *e) {
+        char *end = nullptr;
+        const long long v = strtoll(e, &end, 10);
+        if (end != e && v >= 0) return (int64_t)v;
+    }
+    return kToneWindowFrames;
 }
 
-double pgx_biquad_tone_gain(double w, double sample_rate, double b0, double b1, double b2, double a1, double a2) {
-    long double hr, hi;
-    return (double)tone_response(w, sample_rate, b0, b1, b2, a1, a2, hr, hi);
-}
+// One chain's launch constants: everything of a window launch that does not depend on (out, start, n, state).
+struct TonePlan {
+    ToneArgs a;                  // start is filled in per launch
+    const double *tables;
+    double phase_abs, w_abs;     // |phase0|, |w|: the per-launch range checks
+};
 
-double pgx_biquad_tone_l1(int64_t settle_frames, double b0, double b1, double b2, double a1, double a2) {
-    return tone_l1(settle_frames, b0, b1, b2, a1, a2);
-}
-
-int pgx_biquad_tone(float *out, int64_t start, int64_t n, double sample_rate, double w, double amp, double phase0,
-                    double b0, double b1, double b2, double a1, double a2, const double *tables,
-                    int64_t settle_frames, double *state, double *state_backup) {
-    PGX_REQUIRE_INIT();
-    if (n <= 0) return PGX_OK;
-    PGX_CHECK_ARG(out && tables && state && sample_rate > 0, "pgx_biquad_tone: bad argument");
-    PGX_CHECK_ARG(pgx_biquad_table_doubles() == (size_t)kTabDoubles, "pgx_biquad_tone: table layout changed");
-    PGX_CHECK_ARG(tone_supported(n, settle_frames, w, sample_rate, b0, b1, b2, a1, a2),
-                  "pgx_biquad_tone: chain or block not supported (pgx_biquad_tone_supported)");
-    // the largest phase of the render (and of the frame before it) has to stay in the bounded sine's range
-    const double far = fabs(phase0) + fabs(w) * ((double)(llabs(start) + n + 1) / sample_rate);
-    PGX_CHECK_ARG(far + 4.0 < pgx::kSinFastRange, "pgx_biquad_tone: phase beyond the fast sine range");
+// false: the chain is one pgx_biquad_tone_supported declines whatever the block length
+static bool tone_make_plan(TonePlan &p, double sample_rate, double w, double amp, double phase0, double b0, double b1,
+                           double b2, double a1, double a2, const double *tables, int64_t settle_frames) {
+    if (!tables || !(sample_rate > 0.0)) return false;
+    if (!tone_supported(2 * settle_frames, settle_frames, w, sample_rate, b0, b1, b2, a1, a2)) return false;
     const ToneFilter &f = tone_filter(w, sample_rate, b0, b1, b2, a1, a2);
     // the tone's constants, made once per (w, sample rate) in long double
     static ToneArgs cached;
@@ -295,14 +309,90 @@ int pgx_biquad_tone(float *out, int64_t start, int64_t n, double sample_rate, do
     a.b2 = b2;
     a.a1 = a1;
     a.a2 = a2;
-    a.start = start;
+    a.start = 0;
     a.settle = settle_frames;
+    p.a = a;
+    p.tables = tables;
+    p.phase_abs = fabs(phase0);
+    p.w_abs = fabs(w);
+    return true;
+}
+
+static int tone_launch(const TonePlan &p, float *out, int64_t start, int64_t n, double *state, double *state_backup,
+                       const char *who) {
+    PGX_CHECK_ARG(out && state, std::string(who) + ": bad argument");
+    PGX_CHECK_ARG(pgx_biquad_table_doubles() == (size_t)kTabDoubles, std::string(who) + ": table layout changed");
+    // what of pgx_biquad_tone_supported depends on the block: n >= 2 settle_frames and the phase advance over it
+    PGX_CHECK_ARG(n >= 2 * p.a.settle && p.w_abs * ((double)n / p.a.sr) < pgx::kSinFastRange,
+                  std::string(who) + ": chain or block not supported (pgx_biquad_tone_supported)");
+    // the largest phase of the render (and of the frame before it) has to stay in the bounded sine's range
+    const double far = p.phase_abs + p.w_abs * ((double)(llabs(start) + n + 1) / p.a.sr);
+    PGX_CHECK_ARG(far + 4.0 < pgx::kSinFastRange, std::string(who) + ": phase beyond the fast sine range");
+    ToneArgs a = p.a;
+    a.start = start;
     const int64_t pieces = pgx::ceil_div(n, (int64_t)kTonePiece);
-    PGX_CHECK_ARG(pieces <= 0x7fffffff, "pgx_biquad_tone: block too long");
-    hipLaunchKernelGGL(k_biquad_tone, dim3((unsigned)pieces), dim3(kToneBlock), 0, pgx::stream(), out, n, tables, state,
+    PGX_CHECK_ARG(pieces <= 0x7fffffff, std::string(who) + ": block too long");
+    hipLaunchKernelGGL(k_biquad_tone, dim3((unsigned)pieces), dim3(kToneBlock), 0, pgx::stream(), out, n, p.tables, state,
                        state_backup, a);
     PGX_LAUNCH_CHECK("k_biquad_tone");
     return PGX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pgx_biquad_tone_supported(int64_t n, int64_t settle_frames, double w, double sample_rate, double b0, double b1,
+                              double b2, double a1, double a2) {
+    return tone_supported(n, settle_frames, w, sample_rate, b0, b1, b2, a1, a2) ? 1 : 0;
+}
+
+double pgx_biquad_tone_gain(double w, double sample_rate, double b0, double b1, double b2, double a1, double a2) {
+    long double hr, hi;
+    return (double)tone_response(w, sample_rate, b0, b1, b2, a1, a2, hr, hi);
+}
+
+double pgx_biquad_tone_l1(int64_t settle_frames, double b0, double b1, double b2, double a1, double a2) {
+    return tone_l1(settle_frames, b0, b1, b2, a1, a2);
+}
+
+int64_t pgx_biquad_tone_window_frames(void) {
+    static const int64_t frames = tone_window_frames_env();
+    return frames;
+}
+
+void *pgx_biquad_tone_plan(double sample_rate, double w, double amp, double phase0, double b0, double b1, double b2,
+                           double a1, double a2, const double *tables, int64_t settle_frames) {
+    TonePlan *p = new TonePlan;
+    if (!tone_make_plan(*p, sample_rate, w, amp, phase0, b0, b1, b2, a1, a2, tables, settle_frames)) {
+        delete p;
+        return nullptr;
+    }
+    return p;
+}
+
+int pgx_biquad_tone_plan_free(void *plan) {
+    delete static_cast<TonePlan *>(plan);
+    return PGX_OK;
+}
+
+int pgx_biquad_tone_window(const void *plan, float *out, int64_t start, int64_t n, double *state, double *state_backup) {
+    PGX_REQUIRE_INIT();
+    if (n <= 0) return PGX_OK;
+    PGX_CHECK_ARG(plan, "pgx_biquad_tone_window: no plan");
+    return tone_launch(*static_cast<const TonePlan *>(plan), out, start, n, state, state_backup, "pgx_biquad_tone_window");
+}
+
+int pgx_biquad_tone(float *out, int64_t start, int64_t n, double sample_rate, double w, double amp, double phase0,
+                    double b0, double b1, double b2, double a1, double a2, const double *tables,
+                    int64_t settle_frames, double *state, double *state_backup) {
+    PGX_REQUIRE_INIT();
+    if (n <= 0) return PGX_OK;
+    PGX_CHECK_ARG(out && tables && state && sample_rate > 0, "pgx_biquad_tone: bad argument");
+    TonePlan p;
+    PGX_CHECK_ARG(tone_make_plan(p, sample_rate, w, amp, phase0, b0, b1, b2, a1, a2, tables, settle_frames),
+                  "pgx_biquad_tone: chain or block not supported (pgx_biquad_tone_supported)");
+    return tone_launch(p, out, start, n, state, state_backup, "pgx_biquad_tone");
 }
 
 }  // extern "C"

@@ -44,7 +44,10 @@ AHEAD_FRAMES = int(os.environ.get("PGX_LOOK_AHEAD_FRAMES", str(1 << 25)))      #
 AHEAD_FRAMES_SMALL_GRAPH = int(os.environ.get("PGX_LOOK_AHEAD_FRAMES_SMALL", str(1 << 27)))   # a window root with one or two PEs
                             # under it holds one or two such buffers, not dozens: 4x the frames (3 - 4 PEs: 2x).  C2 over a stream
                             # of 20 000 steps: 883 000 Msamples/s at 2^25, 978 000 at 2^26, 1 045 000 at 2^27 (fewer launch ramps
-                            # and warm-up halves per frame, a quarter of the window openings)
+                            # and warm-up halves per frame, a quarter of the window openings).  That was measured while the
+                            # window kernel was compute-bound.  A window root whose kernel is bound by its stores says so
+                            # itself (`_look_ahead_frames()`, window_blocks below): BiquadPE(SinePE)'s closed-form windows
+                            # are kept small enough for two of them to stay in the memory-side cache.
 _FRAMES_EXPLICIT = "PGX_LOOK_AHEAD_FRAMES" in os.environ
 
 
@@ -53,6 +56,16 @@ def frame_cap(n_nodes: int) -> int:
     if _FRAMES_EXPLICIT or n_nodes > 4:
         return AHEAD_FRAMES
     return max(AHEAD_FRAMES, AHEAD_FRAMES_SMALL_GRAPH if n_nodes <= 2 else AHEAD_FRAMES_SMALL_GRAPH // 2)
+
+
+def window_blocks(grow: int, duration: int, n_nodes: int, hint=None) -> int:
+    """Blocks of `duration` frames in the next window of a stream whose slow start has reached `grow` blocks.  `hint`: the
+    window root's own figure in frames (`_look_ahead_frames()`, None or 0: none) -- one more upper bound, which an
+    explicit PGX_LOOK_AHEAD_FRAMES overrides.  Never fewer than 2 blocks, never more frames than frame_cap."""
+    blocks = min(grow, AHEAD_BLOCKS, frame_cap(n_nodes) // duration)
+    if hint and not _FRAMES_EXPLICIT:
+        blocks = min(blocks, int(hint) // duration)
+    return max(2, blocks)
 
 STATS = {"window_frames": 0, "windows": 0}     # frames rendered into windows since the process started (bench.py reports
                                                # how many frames a timed region really rendered next to those it counts)
@@ -257,7 +270,8 @@ def render(pe, start: int, duration: int):
     # slow start: a stream that stops after a few blocks has not paid for 64; one that keeps going doubles its
     # window with every refill (8, 16, 32, 64 blocks)
     grow = d.get("_la_grow", FIRST_WINDOW_BLOCKS)
-    blocks = max(2, min(grow, AHEAD_BLOCKS, frame_cap(len(nodes)) // duration))
+    hint = getattr(pe, "_look_ahead_frames", None)
+    blocks = window_blocks(grow, duration, len(nodes), hint() if hint is not None else None)
     try:
         big = pe._render(start, duration * blocks)
     except BaseException as exc:

@@ -47,6 +47,26 @@ def launch():
 
 
 timed("pgx_biquad_sine ctypes call (8 M frames)", launch, rep=200, sync_every=10)
+# the closed-form window's two entries at the smallest size class they take: seventeen arguments, and six with a plan
+tone_n = 17_000_000
+tone_out = new_output(tone_n, 1)
+tone_plan = L.pgx_biquad_tone_plan(sr, w, amp, phase, *pe._coef_host, pe._tables.ptr, pe._settle)
+
+
+def launch_tone():
+    L.pgx_biquad_tone(tone_out.ptr, pos[0], tone_n, sr, w, amp, phase, *pe._coef_host, pe._tables.ptr, pe._settle,
+                      pe._state.ptr, bk.ptr)
+    pos[0] += tone_n
+
+
+def launch_tone_window():
+    L.pgx_biquad_tone_window(tone_plan, tone_out.ptr, pos[0], tone_n, pe._state.ptr, bk.ptr)
+    pos[0] += tone_n
+
+
+timed("pgx_biquad_tone ctypes call (17 M frames, 17 arguments)", launch_tone, rep=200, sync_every=4)
+timed("pgx_biquad_tone_window ctypes call (17 M frames, plan)", launch_tone_window, rep=200, sync_every=4)
+L.pgx_biquad_tone_plan_free(tone_plan)
 timed("pgx_stream_is_forked (a trivial ctypes call)", lambda: L.pgx_stream_is_forked())
 timed("Snippet(start, DeviceBuffer)", lambda: Snippet(0, out))
 timed("Snippet.window_rows", lambda: Snippet.window_rows(0, out, 0, frames))
