@@ -10,6 +10,7 @@ with the source tree to the GPU box.
 
 from __future__ import annotations
 
+import glob
 import os
 import subprocess
 import sys
@@ -22,7 +23,10 @@ LIB_PATH = os.environ.get("PGX_LIB_PATH") or os.path.join(PKG_DIR, "libpygmu_hip
 SOURCES = [
     "pgx_runtime.hip",
     "pgx_elementwise.hip",
+    "pgx_biquad.hip",
     "pgx_scan.hip",
+    "pgx_phase.hip",
+    "pgx_envelope.hip",
     "pgx_tone.hip",
     "pgx_seq.hip",
     "pgx_comb.hip",
@@ -59,9 +63,19 @@ def _hipcc() -> str:
 
 
 def _deps_common():
-    return [os.path.join(CSRC, "pgx_common.h"), os.path.join(CSRC, "pgx_pcg.h"),
-            os.path.join(ROOT, "include", "pygmu_hip.h"),
-            os.path.abspath(__file__)]
+    """What the library as a whole depends on besides SOURCES: every header of csrc, the public header, this file."""
+    return sorted(glob.glob(os.path.join(CSRC, "*.h"))) + [os.path.join(ROOT, "include", "pygmu_hip.h"),
+                                                           os.path.abspath(__file__)]
+
+
+def _deps(obj: str, src: str):
+    """What one unit's object depends on: the files the compiler read for it (the depfile written beside the object by
+    -MD), and this file.  An object without a depfile predates this file and is rebuilt."""
+    deps = [src, os.path.abspath(__file__)]
+    if os.path.exists(obj + ".d"):
+        with open(obj + ".d") as f:
+            deps += f.read().replace("\\\n", " ").split(":", 1)[1].split()
+    return deps
 
 
 def _stale(target: str, deps) -> bool:
@@ -118,9 +132,9 @@ def build(force: bool = False, verbose: bool = True) -> str:
         src = os.path.join(CSRC, name)
         obj = os.path.join(obj_dir, name.replace(".hip", ".o"))
         objs.append(obj)
-        if force or _stale(obj, [src] + _deps_common()):
+        if force or _stale(obj, _deps(obj, src)):
             jobs.append([_hipcc()] + compile_flags + ["-I" + os.path.join(ROOT, "include"), "-I" + CSRC,
-                                                      "-c", src, "-o", obj])
+                                                      "-MD", "-MF", obj + ".d", "-c", src, "-o", obj])
 
     def run(cmd):
         if verbose:

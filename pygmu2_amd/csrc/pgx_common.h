@@ -22,7 +22,7 @@ hipStream_t main_stream();   // the stream `stream()` returns outside a fork
 bool initialised();
 int device_index();
 
-// Frees the pacing words of the BiquadPE(SinePE) window kernel (pgx_scan.hip); pgx_shutdown calls it.
+// Frees the pacing words of the BiquadPE(SinePE) window kernel (pgx_biquad.hip); pgx_shutdown calls it.
 void biquad_sine_pacing_release();
 
 }  // namespace pgx

@@ -6,7 +6,7 @@
 //     integers only, so the result is the reference's bit for bit however the stream is cut into workgroups;
 //   * the slew limiter's one-sample update is a continuous, non-decreasing, piecewise-linear map of the carried
 //     value, solved time-parallel by Newton rounds over affine pieces exactly as EnvelopePE's attack != release
-//     follower is (k_env_newton / k_env_newton_mw in pgx_scan.hip, restated here for two other maps);
+//     follower is (k_env_newton / k_env_newton_mw in pgx_envelope.hip, restated here for two other maps);
 //   * the function generator's carried phase is a float64 prefix sum over workgroup segments, the scheme of
 //     pgx_timewarp_scan.
 // float64 inside, float32 at the store.

@@ -1,5 +1,5 @@
 // pgx_elementwise.hip -- stateless per-sample kernels: sources, SinePE (pure), GainPE, MixPE,
-// gates/triggers, SuperSaw voice sum.
+// gates/triggers, SuperSaw voice sum, TransformPE's op chains.
 //
 // All of these are HBM-streaming kernels: each lane owns 4 consecutive float32 output
 // elements (16 B/lane, 1 KiB per wave store), grids are capped at 256 CUs x 8 blocks and
@@ -449,6 +449,31 @@ __global__ void __launch_bounds__(kBlock) k_supersaw_sum(float *out, int64_t out
     }
 }
 
+// ================================================================================================
+// TransformPE: chains of named element-wise float64 operations (pygmu2_amd/transforms.py)
+// ================================================================================================
+__global__ void __launch_bounds__(kBlock)
+k_transform(float *out, const float *in, int64_t n_elems, const pgx_transform_op *ops, int nops) {
+    const int64_t stride = (int64_t)gridDim.x * kBlock;
+    for (int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x; e < n_elems; e += stride) {
+        double v = (double)in[e];
+        for (int k = 0; k < nops; ++k) {
+            const pgx_transform_op op = ops[k];
+            switch (op.code) {
+            case 0: v = op.p1 + op.p0 * v; break;                              // affine: offset + scale*x
+            case 1: v = v < op.p0 ? op.p0 : (v > op.p1 ? op.p1 : v); break;    // clip (NaN passes through)
+            case 2: v = sqrt(v); break;                                        // x ** 0.5 (numpy -> sqrt)
+            case 3: v = v * v; break;                                          // x ** 2 (numpy -> square)
+            case 4: v = fabs(v); break;
+            case 5: v = tanh(v); break;
+            case 6: v = 1.0 - v; break;
+            default: break;
+            }
+        }
+        out[e] = (float)v;
+    }
+}
+
 }  // namespace
 
 // ================================================================================ C ABI
@@ -690,6 +715,16 @@ int pgx_supersaw_sum(float *out, int64_t out_stride, int batch, int nvoices, int
     hipLaunchKernelGGL(k_supersaw_sum, grid, dim3(kBlock), 0, pgx::stream(), out, out_stride, nvoices, n,
                        channels, voices, amp_scalar, amp, amp_stride);
     PGX_LAUNCH_CHECK("k_supersaw_sum");
+    return PGX_OK;
+}
+
+int pgx_transform(float *out, const float *in, int64_t n_elems, const pgx_transform_op *ops, int nops) {
+    PGX_REQUIRE_INIT();
+    if (n_elems <= 0) return PGX_OK;
+    PGX_CHECK_ARG(out && in && (ops || nops == 0) && nops >= 0, "pgx_transform: bad argument");
+    hipLaunchKernelGGL(k_transform, dim3(pgx::grid_for(n_elems, kBlock)), dim3(kBlock), 0, pgx::stream(), out,
+                       in, n_elems, ops, nops);
+    PGX_LAUNCH_CHECK("k_transform");
     return PGX_OK;
 }
 

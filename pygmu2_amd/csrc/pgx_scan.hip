@@ -1,1307 +1,27 @@
-// pgx_scan.hip -- linear-recurrence PEs evaluated as parallel scans over affine state maps.
+// pgx_scan.hip -- what is left of the linear-recurrence PEs' former single unit (the other families: pgx_biquad.hip,
+// pgx_phase.hip, pgx_envelope.hip): the saw family and the time-varying 2x2 recurrences.
 //
-//   BiquadPE (constant)  : 2-state constant map      z' = A z + B x      (biquad_pe.py:383-404)
+//   BlitSawPE            : prefix sum (phase) + 1-state constant map (leaky integrator) (blit_saw_pe.py:150-264); the
+//                          oscillator into a constant BiquadPE (bank, wide, segments), the voice tiles, and SuperSaw
 //   BiquadPE (varying)   : 2-state time-varying map  [y;y1]' = M_n [y1;y2] + [ff_n;0] (biquad_pe.py:35-62)
-//   BlitSawPE            : prefix sum (phase) + 1-state constant map (leaky integrator)
-//                          (blit_saw_pe.py:150-264)
-//   SinePE (stateful)    : prefix sum (phase)        (sine_pe.py:177-232)
 //   SVFilterPE           : 2-state map with a full 2x2 A, constant or per sample (svfilter_pe.py:41-205)
-//   EnvelopePE           : 1-state map; with attack != release a walk over regimes (envelope_pe.py:128-271)
-//   TransformPE          : element-wise op chains (transform_pe.py:96-152) -- no recurrence, kept here
-//                          with the PEs of the same reference script
 //
-// Common structure (wave64, 256-thread workgroups = 4 waves):
-//   * a tile is 256 threads x T consecutive frames; every thread folds its T frames into one
-//     affine map starting from the zero state (pass 1),
-//   * the 64 per-lane maps of a wave are combined with a Kogge-Stone scan over __shfl_up
-//     (6 steps; for constant maps only the offset vector travels, the matrix powers
-//     A^(T*2^k) are loop invariants kept in LDS),
-//   * the 4 wave totals cross through LDS; the tile's carry-out feeds the next tile of the
-//     same chain in registers,
-//   * every thread then re-runs its T frames from its scanned carry-in in EXACTLY the
-//     reference's float64 operation order (pass 2) and stores float32.
-// So the only departure from the reference's sequential float64 arithmetic is the rounding
-// of each chunk's carry-in (O(1e-16) relative); everything is compiled with -ffp-contract=off.
-//
-// Long chains are cut into segments, one workgroup each, in one of three ways:
-//   * constant sections that forget (k_biquad_settled): each workgroup rebuilds its carry-in from a
-//     short warm-up over the frames before its range -- one launch, no cross-workgroup traffic;
-//   * constant sections that decay slowly (k_biquad_const<reduce/apply>): a reduce launch produces every
-//     segment's zero-state response, the apply launch folds the preceding aggregates (binary powers of
-//     A^segment) into its carry-in -- exact for any section;
-//   * time-varying maps (k_biquad_varying / k_svf <reduce/apply>): the reduce launch composes each
-//     segment's affine map, the apply launch folds the earlier maps onto the carried state.
-// Many short chains (voices) use one workgroup per chain and no cross-workgroup traffic at all.
+// Scan primitives: pgx_scan.h; the constant filter's tables: pgx_biquad_tables.h.
 
 #include <cstdlib>
 #include <type_traits>
 
 #include "pgx_common.h"
+#include "pgx_scan.h"
+#include "pgx_biquad_tables.h"
 
 namespace {
-
-constexpr int kBlock = 256;
-constexpr int kWaves = kBlock / 64;
-
-struct V2 {
-    double x, y;
-};
-struct M2 {
-    double a, b, c, d;   // [[a b],[c d]]
-};
-
-__device__ __forceinline__ M2 mm(const M2 &p, const M2 &q) {   // p*q
-    M2 r;
-    r.a = p.a * q.a + p.b * q.c;
-    r.b = p.a * q.b + p.b * q.d;
-    r.c = p.c * q.a + p.d * q.c;
-    r.d = p.c * q.b + p.d * q.d;
-    return r;
-}
-__device__ __forceinline__ V2 mv(const M2 &p, const V2 &v) {
-    V2 r;
-    r.x = p.a * v.x + p.b * v.y;
-    r.y = p.c * v.x + p.d * v.y;
-    return r;
-}
-__device__ __forceinline__ V2 vadd(const V2 &p, const V2 &q) { return V2{p.x + q.x, p.y + q.y}; }
-__device__ __forceinline__ M2 m_identity() { return M2{1.0, 0.0, 0.0, 1.0}; }
-
-__device__ __forceinline__ V2 shfl_up_v2(const V2 &v, int d) {
-    return V2{__shfl_up(v.x, d, 64), __shfl_up(v.y, d, 64)};
-}
-
-__device__ __forceinline__ double readlane_f64(double v, int src_lane) {   // src_lane wave-uniform
-    const int lo = __builtin_amdgcn_readlane(__double2loint(v), src_lane);
-    const int hi = __builtin_amdgcn_readlane(__double2hiint(v), src_lane);
-    return __hiloint2double(hi, lo);
-}
-
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ double dpp_f64_keep(double old, double v) {     // lanes without a source keep `old`
-    const int lo = __builtin_amdgcn_update_dpp(__double2loint(old), __double2loint(v), CTRL, ROW_MASK, 0xf, false);
-    const int hi = __builtin_amdgcn_update_dpp(__double2hiint(old), __double2hiint(v), CTRL, ROW_MASK, 0xf, false);
-    return __hiloint2double(hi, lo);
-}
-// DPP shifts of a 2x2 map / a 2-vector; lanes without a source see the identity map / the zero vector, so a
-// scan step needs no lane test.
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ M2 dpp_m2_identity(const M2 &m) {
-    return M2{dpp_f64_keep<CTRL, ROW_MASK>(1.0, m.a), dpp_f64_keep<CTRL, ROW_MASK>(0.0, m.b),
-              dpp_f64_keep<CTRL, ROW_MASK>(0.0, m.c), dpp_f64_keep<CTRL, ROW_MASK>(1.0, m.d)};
-}
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ V2 dpp_v2_zero(const V2 &v) {
-    return V2{dpp_f64_keep<CTRL, ROW_MASK>(0.0, v.x), dpp_f64_keep<CTRL, ROW_MASK>(0.0, v.y)};
-}
-
-__device__ __forceinline__ bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
-// ------------------------------------------------------------------------------------------------
-// Load / store T consecutive frames of one channel of a (frames, channels) float32 buffer.
-template <int T>
-__device__ __forceinline__ void load_frames(const float *base, int64_t f0, int64_t n, int channels, int ch,
-                                            float (&x)[T]) {
-    if (channels == 1 && f0 + T <= n && aligned16(base + f0)) {
-#pragma unroll
-        for (int j = 0; j < T; j += 4) {
-            float4 t = *reinterpret_cast<const float4 *>(base + f0 + j);
-            x[j] = t.x; x[j + 1] = t.y; x[j + 2] = t.z; x[j + 3] = t.w;
-        }
-    } else {
-#pragma unroll
-        for (int j = 0; j < T; ++j) x[j] = (f0 + j < n) ? base[(f0 + j) * channels + ch] : 0.0f;
-    }
-}
-
-template <int T>
-__device__ __forceinline__ void store_frames(float *base, int64_t f0, int64_t n, int channels, int ch,
-                                             const float (&y)[T]) {
-    if (channels == 1 && f0 + T <= n && aligned16(base + f0)) {
-#pragma unroll
-        for (int j = 0; j < T; j += 4)
-            *reinterpret_cast<float4 *>(base + f0 + j) = make_float4(y[j], y[j + 1], y[j + 2], y[j + 3]);
-    } else {
-#pragma unroll
-        for (int j = 0; j < T; ++j)
-            if (f0 + j < n) base[(f0 + j) * channels + ch] = y[j];
-    }
-}
-
-// Store T frames of a mono result replicated over `channels` output channels (np.tile).
-template <int T>
-__device__ __forceinline__ void store_frames_tiled(float *base, int64_t f0, int64_t n, int channels,
-                                                   const float (&y)[T]) {
-    if (channels == 1) {
-        store_frames<T>(base, f0, n, 1, 0, y);
-    } else {
-#pragma unroll
-        for (int j = 0; j < T; ++j)
-            if (f0 + j < n)
-                for (int c = 0; c < channels; ++c) base[(f0 + j) * channels + c] = y[j];
-    }
-}
-
-// ------------------------------------------------------------------------------------------------
-// Block-wide exclusive prefix sum of one double per thread: pgx::block_excl_sum (pgx_common.h; TimeWarpPE's
-// position scan in pgx_lookup.hip integrates its rate with the same routine).
-__device__ __forceinline__ double block_excl_sum(double v, double *lds, double &total) {
-    return pgx::block_excl_sum<kWaves>(v, lds, total);
-}
-
-// Block-wide scan for the scalar constant map y' = lam^len * y + b.  On entry `e` is this thread's
-// zero-state chunk response; lamp[k] = lam^(T*2^k) for k=0..5, lam_wave = lam^(T*64),
-// lam_lane = lam^(T*lane).  Returns this thread's carry-in given the tile carry-in `carry`, and
-// updates `carry` to the tile carry-out.  `lds` holds kWaves doubles.
-__device__ __forceinline__ double block_scan_scalar_affine(double e, const double (&lamp)[6], double lam_wave,
-                                                           double lam_lane, double *lds, double &carry) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    double inc = e;
-#pragma unroll
-    for (int k = 0; k < 6; ++k) {
-        double o = __shfl_up(inc, 1 << k, 64);
-        if (lane >= (1 << k)) inc = lamp[k] * o + inc;
-    }
-    if (lane == 63) lds[wave] = inc;
-    __syncthreads();
-    double cw = carry, cn = carry;
-#pragma unroll
-    for (int w = 0; w < kWaves; ++w) {
-        double t = lds[w];
-        if (w < wave) cw = lam_wave * cw + t;
-        cn = lam_wave * cn + t;
-    }
-    __syncthreads();
-    carry = cn;
-    double ex = __shfl_up(inc, 1, 64);
-    if (lane == 0) ex = 0.0;
-    return lam_lane * cw + ex;
-}
-
-// Inclusive scans over a wave on DPP moves (VALU; a `__shfl_up` step is two ds_bpermute round trips through LDS):
-// Kogge-Stone inside each 16-lane row (row_shr), then row 0 -> 1 and 2 -> 3 (lane 15 of the previous row), then
-// rows 0-1 -> 2, 3 (lane 31).  Lanes without a source receive the neutral element.  Every oscillator kernel scans
-// with these two, so their folds -- and bits -- agree with each other.
-__device__ __forceinline__ double wave_incl_sum_dpp(double v) {
-    v = dpp_f64_keep<0x111, 0xf>(0.0, v) + v;
-    v = dpp_f64_keep<0x112, 0xf>(0.0, v) + v;
-    v = dpp_f64_keep<0x114, 0xf>(0.0, v) + v;
-    v = dpp_f64_keep<0x118, 0xf>(0.0, v) + v;
-    v = dpp_f64_keep<0x142, 0xa>(0.0, v) + v;
-    v = dpp_f64_keep<0x143, 0xc>(0.0, v) + v;
-    return v;
-}
-// y' = lam^len * y + b: lamp[k] = lam^(T*2^k); lam16 / lam32 = lam^(T*((lane & 15) + 1)) / lam^(T*((lane & 31) + 1))
-__device__ __forceinline__ double wave_incl_affine_dpp(double e, const double (&lamp)[6], double lam16, double lam32) {
-    // (fused multiply-adds: these numbers only feed carries -- the samples themselves are re-run from the scanned
-    // carry-in in the reference's operation order; k_blitsaw_chain folds with the same fused step)
-    e = __builtin_fma(lamp[0], dpp_f64_keep<0x111, 0xf>(0.0, e), e);
-    e = __builtin_fma(lamp[1], dpp_f64_keep<0x112, 0xf>(0.0, e), e);
-    e = __builtin_fma(lamp[2], dpp_f64_keep<0x114, 0xf>(0.0, e), e);
-    e = __builtin_fma(lamp[3], dpp_f64_keep<0x118, 0xf>(0.0, e), e);
-    e = __builtin_fma(lam16, dpp_f64_keep<0x142, 0xa>(0.0, e), e);
-    e = __builtin_fma(lam32, dpp_f64_keep<0x143, 0xc>(0.0, e), e);
-    return e;
-}
-// the per-lane powers of a scan over chunks of T samples, from lamp[k] = lam^(T*2^k)
-struct LanePowers {
-    double lane, p16, p32;      // lam^(T*lane), lam^(T*((lane & 15) + 1)), lam^(T*((lane & 31) + 1))
-};
-__device__ __forceinline__ LanePowers lane_powers(const double (&lamp)[6], int lane) {
-    LanePowers r{1.0, 1.0, 1.0};
-    const int a = (lane & 15) + 1, b = (lane & 31) + 1;
-#pragma unroll
-    for (int k = 0; k < 6; ++k) {
-        if (lane & (1 << k)) r.lane = r.lane * lamp[k];
-        if (a & (1 << k)) r.p16 = r.p16 * lamp[k];
-        if (b & (1 << k)) r.p32 = r.p32 * lamp[k];
-    }
-    return r;
-}
-
-// Wide forms for a workgroup of NW = 4*G waves that must reproduce, bit for bit, what a 4-wave workgroup
-// computes on G consecutive tiles: the wave values are the same, so it is enough to fold them in the same
-// order.  sum_carry: running sum entering the first of the G tiles (advanced to the one leaving the last).
-template <int NW>
-__device__ __forceinline__ double block_excl_sum_wide(double v, double *lds, double &sum_carry) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const double inc = wave_incl_sum_dpp(v);
-    if (lane == 63) lds[wave] = inc;
-    __syncthreads();
-    double base = sum_carry, mine_base = sum_carry, woff = 0.0;
-#pragma unroll
-    for (int g = 0; g < NW / kWaves; ++g) {
-        double tot = 0.0, w_local = 0.0;
-#pragma unroll
-        for (int w = 0; w < kWaves; ++w) {
-            const double t = lds[g * kWaves + w];
-            if (g * kWaves + w < wave) w_local = w_local + t;
-            tot = tot + t;
-        }
-        if (g == wave / kWaves) {
-            mine_base = base;
-            woff = w_local;
-        }
-        base = base + tot;                                   // carry_sum = carry_sum + tile_total
-    }
-    __syncthreads();
-    sum_carry = base;
-    const double ex = dpp_f64_keep<0x138, 0xf>(0.0, inc);   // wave_shr:1 -- the lane before, 0 for lane 0
-    return mine_base + (woff + ex);                          // chunk_base = carry_sum + off
-}
-
-template <int NW>
-__device__ __forceinline__ double block_scan_scalar_affine_wide(double e, const double (&lamp)[6], double lam_wave,
-                                                                double lam_lane, double *lds, double &carry) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    double inc = e;
-#pragma unroll
-    for (int k = 0; k < 6; ++k) {
-        double o = __shfl_up(inc, 1 << k, 64);
-        if (lane >= (1 << k)) inc = lamp[k] * o + inc;
-    }
-    if (lane == 63) lds[wave] = inc;
-    __syncthreads();
-    double cw = carry, cn = carry;
-#pragma unroll
-    for (int w = 0; w < NW; ++w) {
-        double t = lds[w];
-        if (w < wave) cw = lam_wave * cw + t;
-        cn = lam_wave * cn + t;
-    }
-    __syncthreads();
-    carry = cn;
-    double ex = __shfl_up(inc, 1, 64);
-    if (lane == 0) ex = 0.0;
-    return lam_lane * cw + ex;
-}
-
-// block_excl_sum_wide when every thread contributes the SAME value (a scalar-frequency oscillator on a tile
-// whose frames are all live): every wave's total is the same number, so the folds need no exchange and no
-// barrier.  Same operations in the same order as the exchanging form, hence the same bits.
-// The two numbers block_excl_sum_wide_uniform derives from v alone: this thread's offset inside the tile and what the
-// carry advances by per group of kWaves waves.  With them a tile's prefix is `carry + offset` (groups before the
-// thread's own first advance the carry): a caller whose v never changes makes them once -- same operations, same bits.
-struct UniformPrefix {
-    double offset, tot;
-};
-__device__ __forceinline__ UniformPrefix uniform_prefix(double v) {
-    const int wave = threadIdx.x >> 6;
-    const double inc = wave_incl_sum_dpp(v);
-    const double t = readlane_f64(inc, 63);
-    double tot = 0.0, w_local = 0.0;
-#pragma unroll
-    for (int w = 0; w < kWaves; ++w) {
-        if (w < (wave & (kWaves - 1))) w_local = w_local + t;
-        tot = tot + t;
-    }
-    const double ex = dpp_f64_keep<0x138, 0xf>(0.0, inc);
-    return UniformPrefix{w_local + ex, tot};
-}
-template <int NW>
-__device__ __forceinline__ double block_excl_sum_wide_uniform(const UniformPrefix &u, double &sum_carry) {
-    const int wave = threadIdx.x >> 6;
-    double base = sum_carry, mine_base = sum_carry;
-#pragma unroll
-    for (int g = 0; g < NW / kWaves; ++g) {
-        if (g == wave / kWaves) mine_base = base;
-        base = base + u.tot;
-    }
-    sum_carry = base;
-    return mine_base + u.offset;
-}
-template <int NW>
-__device__ __forceinline__ double block_excl_sum_wide_uniform(double v, double &sum_carry) {
-    return block_excl_sum_wide_uniform<NW>(uniform_prefix(v), sum_carry);
-}
-
-// block_scan_scalar_affine_wide with ONE barrier: `lds` holds two images of NW doubles used alternately
-// (`parity` flips on every call), so the readers of one image are separated from its next writer by the
-// barrier of the call in between.
-template <int NW>
-__device__ __forceinline__ double block_scan_scalar_affine_wide1(double e, const double (&lamp)[6], double lam_wave,
-                                                                 const LanePowers &lp, double *lds, int parity,
-                                                                 double &carry) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    double *img = lds + (parity & 1) * NW;
-    const double inc = wave_incl_affine_dpp(e, lamp, lp.p16, lp.p32);
-    if (lane == 63) img[wave] = inc;
-    __syncthreads();
-    double cw = carry, cn = carry;
-#pragma unroll
-    for (int w = 0; w < NW; ++w) {
-        double t = img[w];
-        if (w < wave) cw = __builtin_fma(lam_wave, cw, t);
-        cn = __builtin_fma(lam_wave, cn, t);
-    }
-    carry = cn;
-    const double ex = dpp_f64_keep<0x138, 0xf>(0.0, inc);
-    return __builtin_fma(lp.lane, cw, ex);
-}
-
-// ================================================================================================
-// BiquadPE, constant coefficients
-// ================================================================================================
-constexpr int kBqT = 16;                       // frames per thread per tile
-constexpr int kBqTile = kBlock * kBqT;         // 4096 frames
-constexpr int kBqMaxSeg = 1024;
-constexpr int kBqPow = 11;                     // binary powers of A^segment kept for the fold
-
-struct BqShared {
-    M2 pstep[6];       // A^(T*2^k)
-    M2 pwave;          // A^(T*64)
-    M2 ptile;          // A^(T*256)
-    M2 pseg[kBqPow];   // (A^segment)^(2^k)
-    V2 wave_tot[kWaves];
-    V2 red[kWaves];
-};
-
-// MODE 0: reduce (write the segment's zero-state response to agg); MODE 1: apply (produce output).
-template <int MODE>
-__global__ void __launch_bounds__(kBlock)
-k_biquad_const(float *out, int64_t out_stride, const float *in, int64_t in_stride, int64_t n, int channels,
-               const double *coef, double *state, const double *state_snapshot, double *agg, int seg_tiles,
-               int nseg) {
-    __shared__ BqShared sh;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int chain = blockIdx.y;
-    const int inst = chain / channels, ch = chain - inst * channels;
-    const int seg = blockIdx.x;
-
-    const double b0 = coef[inst * 5 + 0], b1 = coef[inst * 5 + 1], b2 = coef[inst * 5 + 2];
-    const double a1 = coef[inst * 5 + 3], a2 = coef[inst * 5 + 4];
-
-    // ---- loop-invariant matrix powers (thread 0 -> LDS) ----
-    if (tid == 0) {
-        M2 A{-a1, 1.0, -a2, 0.0};
-        M2 p = A;
-#pragma unroll
-        for (int s = 1; s < kBqT; s <<= 1) p = mm(p, p);     // A^T (T is a power of two)
-        for (int k = 0; k < 6; ++k) {
-            sh.pstep[k] = p;
-            p = mm(p, p);
-        }
-        sh.pwave = p;                                        // A^(64 T)
-        p = mm(p, p);
-        p = mm(p, p);
-        sh.ptile = p;                                        // A^(256 T)
-        if (nseg > 1) {
-            // A^segment = ptile^seg_tiles (binary exponentiation), then its binary powers.
-            M2 r = m_identity(), q = p;
-            for (int e = seg_tiles; e > 0; e >>= 1) {
-                if (e & 1) r = mm(r, q);
-                q = mm(q, q);
-            }
-            for (int k = 0; k < kBqPow; ++k) {
-                sh.pseg[k] = r;
-                r = mm(r, r);
-            }
-        }
-    }
-    __syncthreads();
-
-    M2 mlane = m_identity();                                  // A^(T*lane)
-#pragma unroll
-    for (int k = 0; k < 6; ++k)
-        if (lane & (1 << k)) mlane = mm(sh.pstep[k], mlane);
-
-    // ---- segment carry-in ----
-    V2 carry{0.0, 0.0};
-    if (MODE == 1) {
-        if (nseg == 1) {
-            carry = V2{state[chain * 2 + 0], state[chain * 2 + 1]};
-        } else {
-            // carry = (A^seg)^seg_index * z_init + sum_{j<seg} (A^seg)^(seg-1-j) * agg_j
-            V2 part{0.0, 0.0};
-            for (int j = tid; j <= seg; j += kBlock) {
-                V2 v;
-                int e;
-                if (j == seg) {                               // the initial-state term
-                    v = V2{state_snapshot[chain * 2 + 0], state_snapshot[chain * 2 + 1]};
-                    e = seg;
-                } else {
-                    v = V2{agg[((int64_t)chain * nseg + j) * 2 + 0], agg[((int64_t)chain * nseg + j) * 2 + 1]};
-                    e = seg - 1 - j;
-                }
-                for (int k = 0; k < kBqPow; ++k)
-                    if (e & (1 << k)) v = mv(sh.pseg[k], v);
-                part = vadd(part, v);
-            }
-#pragma unroll
-            for (int d = 32; d > 0; d >>= 1) {
-                part.x += __shfl_down(part.x, d, 64);
-                part.y += __shfl_down(part.y, d, 64);
-            }
-            if (lane == 0) sh.red[wave] = part;
-            __syncthreads();
-            carry = V2{0.0, 0.0};
-#pragma unroll
-            for (int w = 0; w < kWaves; ++w) carry = vadd(carry, sh.red[w]);
-            __syncthreads();
-        }
-    }
-
-    const float *ib = in + (int64_t)inst * in_stride;
-    float *ob = out + (int64_t)inst * out_stride;
-    V2 final_state{0.0, 0.0};
-    bool have_final = false;
-
-    const int64_t tile0 = (int64_t)seg * seg_tiles;
-    for (int t = 0; t < seg_tiles; ++t) {
-        const int64_t base = (tile0 + t) * kBqTile;
-        if (base >= n) break;
-        const int64_t f0 = base + (int64_t)tid * kBqT;
-        float xf[kBqT];
-        load_frames<kBqT>(ib, f0, n, channels, ch, xf);
-
-        // pass 1: zero-state response of this chunk
-        V2 e{0.0, 0.0};
-#pragma unroll
-        for (int j = 0; j < kBqT; ++j) {
-            double x = (double)xf[j];
-            double y = e.x + b0 * x;
-            double z0 = (e.y + b1 * x) - a1 * y;
-            e.y = b2 * x - a2 * y;
-            e.x = z0;
-        }
-        // wave scan (offset vectors only; the matrices are the LDS-resident powers)
-#pragma unroll
-        for (int k = 0; k < 6; ++k) {
-            V2 o = shfl_up_v2(e, 1 << k);
-            if (lane >= (1 << k)) e = vadd(mv(sh.pstep[k], o), e);
-        }
-        if (lane == 63) sh.wave_tot[wave] = e;
-        __syncthreads();
-        V2 cw = carry, cn = carry;
-#pragma unroll
-        for (int w = 0; w < kWaves; ++w) {
-            V2 tot = sh.wave_tot[w];
-            if (w < wave) cw = vadd(mv(sh.pwave, cw), tot);
-            cn = vadd(mv(sh.pwave, cn), tot);
-        }
-        __syncthreads();
-        carry = cn;
-
-        if (MODE == 1) {
-            V2 ex = shfl_up_v2(e, 1);
-            if (lane == 0) ex = V2{0.0, 0.0};
-            V2 z = vadd(mv(mlane, cw), ex);
-            float yf[kBqT];
-            // pass 2: scipy lfilter DF-II-T operation order from the scanned carry-in
-#pragma unroll
-            for (int j = 0; j < kBqT; ++j) {
-                double x = (double)xf[j];
-                double y = z.x + b0 * x;
-                double z0 = (z.y + b1 * x) - a1 * y;
-                z.y = b2 * x - a2 * y;
-                z.x = z0;
-                yf[j] = (float)y;
-                if (f0 + j == n - 1) {
-                    final_state = z;
-                    have_final = true;
-                }
-            }
-            store_frames<kBqT>(ob, f0, n, channels, ch, yf);
-        }
-    }
-    if (MODE == 0) {
-        if (tid == 0) {
-            agg[((int64_t)chain * nseg + seg) * 2 + 0] = carry.x;
-            agg[((int64_t)chain * nseg + seg) * 2 + 1] = carry.y;
-            if (seg == 0) {
-                // snapshot of the carried state for the apply launch (whose last segment overwrites
-                // `state` while other segments may not have started yet)
-                double *snap = const_cast<double *>(state_snapshot);
-                snap[chain * 2 + 0] = state[chain * 2 + 0];
-                snap[chain * 2 + 1] = state[chain * 2 + 1];
-            }
-        }
-    } else if (have_final) {
-        state[chain * 2 + 0] = final_state.x;
-        state[chain * 2 + 1] = final_state.y;
-    }
-}
-
-// ------------------------------------------------------------------------------------------------
-// Settled single launch.  A stable section forgets: once every entry of A^W is below 2^-90 the state W
-// frames back no longer reaches the float64 arithmetic of the present.  Each workgroup then recovers
-// its carry-in by running the recurrence from zero over the frames that precede its range (outputs
-// discarded) instead of waiting for its predecessors: one launch, no cross-workgroup traffic, every
-// input frame fetched from HBM once (the warm-up frames are L2/MALL hits of a neighbour's fetch).
-// W is evaluated by the host from the coefficients (pgx_biquad_const's settle_frames); slowly decaying
-// sections (W above kSbMaxWarm half-tiles) keep the exact reduce + apply pair.
-//
-// Geometry: 512 threads x 16 frames = one 8192-frame tile, addressed in 4096-frame halves so that the
-// smallest plan (one half of warm-up + one half of output per workgroup) is a single scan step.
-// Workgroup 0 renders the halves [0, head) and the tail [tail_start, halves): it alone reads the
-// carried state (first thing) and writes it (last thing); workgroup g >= 1 renders seg halves from
-// head + (g-1)*seg.  head >= warm, so no other workgroup ever needs the carried state.
-// ------------------------------------------------------------------------------------------------
-constexpr int kSbBlock = 512;
-constexpr int kSbWaves = kSbBlock / 64;
-constexpr int kSbHalf = (kSbBlock / 2) * kBqT;     // 4096 frames
-constexpr int kSbMaxWarm = 16;                     // half-tiles
-
-// DPP moves of a double (two 32-bit halves).  CTRL: 0x110+n = row_shr:n (within 16-lane rows),
-// 0x138 = wave_shr:1, 0x142 = row_bcast:15, 0x143 = row_bcast:31.  Lanes without a source, or outside
-// ROW_MASK, receive 0.0.
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ double dpp_f64(double v) {
-    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, ROW_MASK, 0xf, false);
-    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, ROW_MASK, 0xf, false);
-    return __hiloint2double(hi, lo);
-}
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ V2 dpp_v2(const V2 &v) {
-    return V2{dpp_f64<CTRL, ROW_MASK>(v.x), dpp_f64<CTRL, ROW_MASK>(v.y)};
-}
-
-struct SbShared {
-    V2 wave_tot[2][kSbWaves];        // two images used in turn: one barrier per tile (the readers of one image are
-};                                   // separated from its next writer by the barrier of the tile in between)
-
-// Staging of a wave's 1024 frames through wave-private LDS: HBM is touched with fully coalesced 16-byte
-// accesses (lane l of access i owns frames i*256 + 4l ..), the scan wants 16 consecutive frames per lane.
-// Chunk c (16 frames) lives at word c*20: the 4-word pad makes both access patterns bank-conflict free.
-constexpr int kStageWords = 64 * 20;
-
-__device__ __forceinline__ void stage_fetch(const float *src, int lane, float (&t)[kBqT]) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const float4 v = *reinterpret_cast<const float4 *>(src + i * 256 + lane * 4);
-        t[4 * i] = v.x; t[4 * i + 1] = v.y; t[4 * i + 2] = v.z; t[4 * i + 3] = v.w;
-    }
-}
-__device__ __forceinline__ int stage_slot(int i, int lane) {       // LDS word of frame i*256 + 4*lane
-    const int idx = i * 256 + lane * 4;
-    return (idx >> 4) * 20 + (idx & 15);
-}
-// coalesced order (as fetched) -> 16 consecutive frames per lane
-__device__ __forceinline__ void stage_to_chunks(float *lds, int lane, float (&t)[kBqT]) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-        *reinterpret_cast<float4 *>(lds + stage_slot(i, lane)) = make_float4(t[4 * i], t[4 * i + 1], t[4 * i + 2], t[4 * i + 3]);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const float4 v = *reinterpret_cast<const float4 *>(lds + lane * 20 + 4 * i);
-        t[4 * i] = v.x; t[4 * i + 1] = v.y; t[4 * i + 2] = v.z; t[4 * i + 3] = v.w;
-    }
-}
-// 16 consecutive frames per lane -> coalesced stores
-__device__ __forceinline__ void stage_store(float *lds, float *dst, int lane, const float (&y)[kBqT]) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-        *reinterpret_cast<float4 *>(lds + lane * 20 + 4 * i) = make_float4(y[4 * i], y[4 * i + 1], y[4 * i + 2], y[4 * i + 3]);
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-        *reinterpret_cast<float4 *>(dst + i * 256 + lane * 4) = *reinterpret_cast<const float4 *>(lds + stage_slot(i, lane));
-}
-
-// Matrix-power tables of one section, computed once per coefficient set (pgx_biquad_tables):
-// A^(16*2^k) for k = 0..5, A^(16*64), then A^(16*j) for j = 0..63.
-constexpr int kBqTableDoubles = 28 + 4 * 64 + 2 * kBqT;     // ... then the first rows of A^j, j = 0..kBqT-1 (SINE pass 2)
-constexpr int kBqRowsAt = 28 + 4 * 64;
-
-__global__ void __launch_bounds__(64)
-k_biquad_tables(double *tables, const double *coef) {
-    __shared__ M2 ps[6];
-    const int lane = threadIdx.x, inst = blockIdx.x;
-    double *tb = tables + (int64_t)inst * kBqTableDoubles;
-    if (lane == 0) {
-        M2 p{-coef[inst * 5 + 3], 1.0, -coef[inst * 5 + 4], 0.0};
-#pragma unroll
-        for (int s = 1; s < kBqT; s <<= 1) p = mm(p, p);
-        for (int k = 0; k < 6; ++k) {
-            ps[k] = p;
-            tb[4 * k] = p.a; tb[4 * k + 1] = p.b; tb[4 * k + 2] = p.c; tb[4 * k + 3] = p.d;
-            p = mm(p, p);
-        }
-        tb[24] = p.a; tb[25] = p.b; tb[26] = p.c; tb[27] = p.d;
-    }
-    __syncthreads();
-    M2 m = m_identity();
-#pragma unroll
-    for (int k = 0; k < 6; ++k)
-        if (lane & (1 << k)) m = mm(ps[k], m);
-    double *ml = tb + 28 + 4 * lane;
-    ml[0] = m.a; ml[1] = m.b; ml[2] = m.c; ml[3] = m.d;
-    if (lane == 0) {
-        // first rows of A^j: what a carried state z contributes to the output of the j-th frame after it, y_h[j] =
-        // (A^j z).x (the sine-source variant adds it to the zero-state outputs it kept from pass 1)
-        M2 q = m_identity();
-        const M2 a1m{-coef[inst * 5 + 3], 1.0, -coef[inst * 5 + 4], 0.0};
-        for (int j = 0; j < kBqT; ++j) {
-            tb[kBqRowsAt + 2 * j] = q.a;
-            tb[kBqRowsAt + 2 * j + 1] = q.b;
-            q = mm(a1m, q);
-        }
-    }
-}
-
-__device__ __forceinline__ M2 load_m2(const double *p) { return M2{p[0], p[1], p[2], p[3]}; }
-
-// p*v + q with fused multiply-adds.  Used only where the result feeds a carry (zero-state responses and
-// their scan), never in the output pass, whose operation order is the reference's.
-__device__ __forceinline__ V2 mv_add_fma(const M2 &p, const V2 &v, const V2 &q) {
-    return V2{__builtin_fma(p.a, v.x, __builtin_fma(p.b, v.y, q.x)),
-              __builtin_fma(p.c, v.x, __builtin_fma(p.d, v.y, q.y))};
-}
-
-// SINE: the input is a pure SinePE (sine_pe.py:159-175) generated in registers instead of read from HBM: the chain
-// BiquadPE(SinePE) then moves 4 B per frame (its output) in one launch.  A thread's first frame is evaluated exactly
-// as k_sine evaluates it (phase0 + w * (n / sr), pgx_sincos_bounded); its other 15 frames turn that (sin, cos) pair
-// by the fixed angle w / sr (two multiplies and two fused multiply-adds per frame, error ~1e-16 per step).  The
-// reference's own phase carries ~ulp(phase) of rounding noise per sample; the rotated samples sit inside it.
-struct SbSine {
-    double w, amp, phase0, sr, inv_sr, cos_d, sin_d;
-    double two_cos_d;          // 2 cos(w / sr) for the three-term recurrence, or 0: rotate (very low frequencies)
-    double tile_cos, tile_sin; // cos / sin of a tile's advance, BLOCK * 16 frames of w / sr (the angle reduced on the host)
-    int64_t start;
-    double *state_backup;      // receives the carried state on entry (a look-ahead window's snapshot), or nullptr
-};
-
-#ifndef PGX_SB_SINE_WAVES
-#define PGX_SB_SINE_WAVES 3        // waves per SIMD the sine-source variant is compiled for: 166 VGPRs, no spill (4: 128 + 28 B of scratch per lane, 6 MB of extra HBM traffic per 33 M frames and 5 % slower)
-#endif
-// BLOCK: threads per workgroup -- 512 (a tile = two halves), or 256 for the sine-source variant (a tile = one half: at its
-// 166 VGPRs a CU holds one 8-wave workgroup, whose single barrier per tile then idles the whole CU, or three 4-wave ones)
-template <bool MONO, bool STAGED, bool SINE = false, int BLOCK = kSbBlock>
-__global__ void __launch_bounds__(BLOCK, MONO ? (SINE ? PGX_SB_SINE_WAVES : 4) : 2)
-k_biquad_settled(float *__restrict__ out, int64_t out_stride, const float *__restrict__ in, int64_t in_stride,
-                 int64_t n, int channels_arg, const double *__restrict__ coef, const double *__restrict__ tables,
-                 double *state, int seg, int head, int tail, int warm, int groups, SbSine sine = SbSine{}) {
-    constexpr int kTileHalves = BLOCK * kBqT / kSbHalf;         // halves a tile covers: 2, or 1
-    __shared__ SbShared sh;
-    __shared__ __attribute__((aligned(16))) float stage_lds[STAGED ? (BLOCK / 64) * kStageWords : 4];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int channels = MONO ? 1 : channels_arg;
-    const int chain = blockIdx.y;
-    const int inst = chain / channels, ch = MONO ? 0 : chain - inst * channels;
-    // Workgroups are dealt to the 8 XCDs round-robin and each XCD has its own L2.  While the warm-up is
-    // a sizeable part of a segment, give every XCD one contiguous run of segments, so that a segment's
-    // warm-up frames are its left neighbour's L2 lines (measured: 1M frames fetch 4.3 MB instead of 8.2 MB).
-    // Long segments keep the round-robin order (the re-read is ~3% there and it streams ~10% faster).
-    const int per_xcd = gridDim.x >> 3;                        // gridDim.x is a multiple of 8
-    const int g = seg <= 8 ? (blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3) : blockIdx.x;
-    if (g >= groups) return;
-    const float *ib = in + (int64_t)inst * in_stride;
-    float *ob = out + (int64_t)inst * out_stride;
-    float *wlds = stage_lds + (STAGED ? wave * kStageWords : 0);
-    // STAGED (mono only): a wave whose 1024 frames are all inside the block and 16-byte aligned moves them
-    // with coalesced accesses; any other wave takes the per-lane path.  `xn_staged` says which layout xn has.
-    const bool io_aligned = STAGED && (SINE || aligned16(ib)) && aligned16(ob);
-    bool xn_staged = false;
-    const int64_t halves = (n + kSbHalf - 1) / kSbHalf;
-    int64_t tail_start = halves - tail;
-    if (tail_start < head) tail_start = head;
-
-    // the ranges of this workgroup, in halves: [hb0, he0) and, for workgroup 0 only, [hb1, he1)
-    int64_t hb = g == 0 ? 0 : head + (int64_t)(g - 1) * seg;
-    int64_t he = g == 0 ? (head < halves ? head : halves) : (hb + seg < tail_start ? hb + seg : tail_start);
-    int64_t h = hb == 0 ? 0 : hb - warm;
-    int64_t emit_to = he * kSbHalf < n ? he * kSbHalf : n;
-
-    // first tile's frames are requested before anything else so that their latency covers the table loads
-    float xn[kBqT];
-    int64_t anchor_tile = -(int64_t)1 << 40;                   // SINE: the tile the anchor (sin, cos) below belongs to
-    double anchor_s = 0.0, anchor_c = 1.0;
-    auto request = [&](int64_t hh) {
-        const int64_t w0 = hh * kSbHalf + (int64_t)(tid - lane) * kBqT;      // first frame of this wave
-        const int64_t f0 = w0 + lane * kBqT;
-        if (SINE) {
-            xn_staged = false;
-            // The thread's first frame: k_sine's evaluation for the first tile of a run of consecutive tiles, that pair
-            // turned by a tile's advance for every further one (4 operations instead of the division and the sincos, ~35;
-            // a workgroup's run is a dozen tiles: ~1e-15).
-            double sn, cs;
-            if (PGX_HOT(hh == anchor_tile + kTileHalves)) {
-                sn = __builtin_fma(anchor_s, sine.tile_cos, anchor_c * sine.tile_sin);
-                cs = __builtin_fma(anchor_c, sine.tile_cos, -(anchor_s * sine.tile_sin));
-            } else {
-                const double t = pgx::pgx_div_by((double)(sine.start + f0), sine.sr, sine.inv_sr);
-                pgx::pgx_sincos_bounded(sine.phase0 + sine.w * t, sn, cs);
-            }
-            anchor_tile = hh;
-            anchor_s = sn;
-            anchor_c = cs;
-            if (PGX_HOT(sine.two_cos_d != 0.0)) {
-                // three-term recurrence sin(p + (j+1)d) = 2 cos(d) sin(p + jd) - sin(p + (j-1)d): ONE fused multiply-add
-                // per frame instead of the four operations of the rotation (the cosine is not needed).  Its error
-                // after k steps is <= k ulp / d: 15 steps, d >= 1e-3 (the host's condition) -> below 2e-12
-                double s0 = sn, s1 = __builtin_fma(cs, sine.sin_d, sn * sine.cos_d);
-#ifndef PGX_C2_NO_UNIT_AMP
-                if (PGX_HOT(sine.amp == 1.0)) {
-                    // SinePE's default amplitude (C2's): amp * s is s, bit for bit -- sixteen multiplications a tile less
-                    // (a wave-uniform choice: sine.amp is a kernel argument)
-                    xn[0] = (float)s0;
-                    xn[1] = (float)s1;
-#pragma unroll
-                    for (int j = 2; j < kBqT; ++j) {
-                        const double s2 = __builtin_fma(sine.two_cos_d, s1, -s0);
-                        xn[j] = (float)s2;
-                        s0 = s1;
-                        s1 = s2;
-                    }
-                    return;
-                }
-#endif
-                xn[0] = (float)(sine.amp * s0);
-                xn[1] = (float)(sine.amp * s1);
-#pragma unroll
-                for (int j = 2; j < kBqT; ++j) {
-                    const double s2 = __builtin_fma(sine.two_cos_d, s1, -s0);
-                    xn[j] = (float)(sine.amp * s2);
-                    s0 = s1;
-                    s1 = s2;
-                }
-                return;
-            }
-#pragma unroll
-            for (int j = 0; j < kBqT; ++j) {
-                xn[j] = (float)(sine.amp * sn);
-                const double s2 = __builtin_fma(cs, sine.sin_d, sn * sine.cos_d);
-                cs = __builtin_fma(-sn, sine.sin_d, cs * sine.cos_d);
-                sn = s2;
-            }
-            return;
-        }
-        xn_staged = STAGED && PGX_HOT(io_aligned && w0 + 64 * kBqT <= emit_to);
-        if (xn_staged) {
-            stage_fetch(ib + w0, lane, xn);
-        } else if (f0 < emit_to) {
-            load_frames<kBqT>(ib, f0, n, channels, ch, xn);
-        } else {
-#pragma unroll
-            for (int j = 0; j < kBqT; ++j) xn[j] = 0.0f;
-        }
-    };
-    if (!SINE && hb < he) request(h);
-
-    const double b0 = coef[inst * 5 + 0], b1 = coef[inst * 5 + 1], b2 = coef[inst * 5 + 2];
-    const double a1 = coef[inst * 5 + 3], a2 = coef[inst * 5 + 4];
-    // uniform loads -> scalar registers
-    const double *tb = tables + (int64_t)inst * kBqTableDoubles;
-    M2 pstep[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) pstep[k] = load_m2(tb + 4 * k);
-    const M2 pwave = load_m2(tb + 24);
-    // per-lane powers: carry-in of the wave -> lane, previous row(s) -> lane
-    const M2 mlane = load_m2(tb + 28 + 4 * lane);
-    const M2 m16 = load_m2(tb + 28 + 4 * ((lane & 15) + 1));
-    const M2 m32 = load_m2(tb + 28 + 4 * ((lane & 31) + 1));
-    // SINE: the first rows of A^j (pass 2) live in LDS, read as broadcasts where they are used.  As 32 uniform values in
-    // scalar registers they did not fit beside the scan's matrices: the compiler parked them in the lanes of a vector
-    // register and fetched them back with 64 v_readlane per tile -- a sixth of the loop's vector instructions (end of round 4)
-    __shared__ __attribute__((aligned(16))) double rows_lds[SINE ? 2 * kBqT : 2];
-    if (SINE) {
-        if (tid < 2 * kBqT) rows_lds[tid] = tb[kBqRowsAt + tid];
-        __syncthreads();
-    }
-
-    int image = 0;
-#pragma nounroll
-    for (int range = 0; range < 2; ++range) {
-        if (range == 1) {
-            if (g != 0) break;
-            hb = tail_start;
-            he = halves;
-            if (hb >= he) break;
-            h = hb - warm;
-            emit_to = n;
-            if (!SINE) request(h);
-        }
-        if (hb >= he) continue;
-        V2 carry{0.0, 0.0};
-        if (hb == 0) {
-            carry = V2{state[chain * 2 + 0], state[chain * 2 + 1]};
-            if (SINE && sine.state_backup && tid == 0) {          // workgroup 0 alone reads and writes the state
-                sine.state_backup[chain * 2 + 0] = carry.x;
-                sine.state_backup[chain * 2 + 1] = carry.y;
-            }
-        }
-        const int64_t emit_from = hb * kSbHalf;
-
-#pragma nounroll
-        for (; h < he; h += kTileHalves) {
-            const int64_t f0 = h * kSbHalf + (int64_t)tid * kBqT;
-            float xf[kBqT];
-            if (SINE) {
-                request(h);                                    // generated, not fetched: nothing to have in flight
-#pragma unroll
-                for (int j = 0; j < kBqT; ++j) xf[j] = xn[j];
-            } else {
-#pragma unroll
-                for (int j = 0; j < kBqT; ++j) xf[j] = xn[j];
-                if (STAGED && xn_staged) stage_to_chunks(wlds, lane, xf);
-                if (h + kTileHalves < he) request(h + kTileHalves);                // next tile's frames, in flight during this one
-            }
-            // zero-state response of the 16-frame chunk
-            V2 e{0.0, 0.0};
-            const double na1 = -a1, na2 = -a2;
-            double yz[SINE ? kBqT : 1];                        // SINE: the zero-state outputs stay for pass 2
-#pragma unroll
-            for (int j = 0; j < kBqT; ++j) {
-                const double x = (double)xf[j];
-                const double y = __builtin_fma(b0, x, e.x);
-                e.x = __builtin_fma(na1, y, __builtin_fma(b1, x, e.y));
-                e.y = __builtin_fma(na2, y, b2 * x);
-                if (SINE) yz[j] = y;
-            }
-            if (!SINE) {
-#pragma unroll
-                for (int j = 0; j < kBqT; ++j) asm volatile("" : "+v"(xf[j]));   // re-convert in pass 2, keep VGPRs low
-            }
-            // inclusive scan over the wave: Kogge-Stone inside each 16-lane row (DPP row shifts) ...
-            e = mv_add_fma(pstep[0], dpp_v2<0x111, 0xf>(e), e);
-            e = mv_add_fma(pstep[1], dpp_v2<0x112, 0xf>(e), e);
-            e = mv_add_fma(pstep[2], dpp_v2<0x114, 0xf>(e), e);
-            e = mv_add_fma(pstep[3], dpp_v2<0x118, 0xf>(e), e);
-            // ... then row 0 -> 1, row 2 -> 3 (lane 15 of the previous row), then rows 0-1 -> 2, 3 (lane 31)
-            e = mv_add_fma(m16, dpp_v2<0x142, 0xa>(e), e);
-            e = mv_add_fma(m32, dpp_v2<0x143, 0xc>(e), e);
-            V2 *tot = sh.wave_tot[image];
-            image ^= 1;
-            if (lane == 63) tot[wave] = e;
-            __syncthreads();
-            V2 cw = carry, run = carry;
-#pragma unroll
-            for (int w = 0; w < BLOCK / 64; ++w) {
-                run = mv_add_fma(pwave, run, tot[w]);
-                if (w + 1 == wave) cw = run;                   // wave-uniform pick of this wave's carry-in
-            }
-#ifdef PGX_SB_TWO_BARRIERS
-            __syncthreads();
-#endif
-            carry = run;
-
-            if (PGX_HOT(f0 >= emit_from && f0 < emit_to)) {
-                const V2 ex = dpp_v2<0x138, 0xf>(e);           // previous lane's inclusive value, 0 for lane 0
-                const V2 zin = mv_add_fma(mlane, cw, ex);
-                V2 z = zin;
-                float yf[kBqT];
-                if (SINE) {
-                    // the zero-state outputs of pass 1 plus what the carried state adds, (A^j zin).x: two
-                    // multiply-adds per frame instead of the recurrence again (the sine chain is within the rounding
-                    // noise of the reference's phase anyway; the plain filter below keeps scipy's operation order)
-                    const double *rows = rows_lds;               // (LDS broadcasts: see above)
-#pragma unroll
-                    for (int j = 0; j < kBqT; ++j)
-                        yf[j] = (float)__builtin_fma(rows[2 * j], zin.x, __builtin_fma(rows[2 * j + 1], zin.y, yz[j]));
-                } else {
-                // scipy lfilter DF-II-T operation order from the scanned carry-in
-#pragma unroll
-                for (int j = 0; j < kBqT; ++j) {
-                    double x = (double)xf[j];
-                    double y = z.x + b0 * x;
-                    double z0 = (z.y + b1 * x) - a1 * y;
-                    z.y = b2 * x - a2 * y;
-                    z.x = z0;
-                    yf[j] = (float)y;
-                }
-                }
-                const int64_t w0 = f0 - lane * kBqT;
-                if (STAGED && PGX_HOT(io_aligned && w0 >= emit_from && w0 + 64 * kBqT <= emit_to))
-                    stage_store(wlds, ob + w0, lane, yf);
-                else
-                    store_frames<kBqT>(ob, f0, n, channels, ch, yf);
-                if (PGX_COLD(n - 1 - f0 < kBqT)) {               // the chunk holding the last frame: new state
-                    z = zin;
-                    for (int j = 0; j <= (int)(n - 1 - f0); ++j) {
-                        double x = (double)xf[j];
-                        double y = z.x + b0 * x;
-                        double z0 = (z.y + b1 * x) - a1 * y;
-                        z.y = b2 * x - a2 * y;
-                        z.x = z0;
-                    }
-                    state[chain * 2 + 0] = z.x;
-                    state[chain * 2 + 1] = z.y;
-                }
-            }
-        }
-    }
-}
-
-// ------------------------------------------------------------------------------------------------
-// Wave runs: BiquadPE(SinePE) over window-sized blocks (pgx_biquad_sine when every wave gets a long run).
-// The filter forgets (settle_frames), so a wave needs no carry-in from any other wave: each wave owns a contiguous
-// run of 1024-frame chunks (64 lanes x 16 frames), warms up from zero state over the `warm` chunks in front of it
-// (outputs discarded) and carries its own state from chunk to chunk, A^1024 carry + e(lane 63): a readlane and four
-// fused multiply-adds.  No barrier and no LDS exchange between waves, so the waves of a CU overlap freely; the grid
-// is one resident round (the occupancy the runtime reports), so there is no tail round either.
-// Per chunk the arithmetic is k_biquad_settled<.., SINE>'s: the same sine, zero-state pass, DPP row scan and pass 2.
-// Wave 0 renders the chunks [0, head) and the tail [tail_start, chunks): it alone reads the carried state (first
-// thing) and writes it (last thing).  Wave g >= 1 renders `run` chunks from head + (g-1)*run.  head >= warm.
-// ------------------------------------------------------------------------------------------------
-struct SbRuns {
-    double w, amp, phase0, sr, inv_sr, cos_d, sin_d;
-    double two_cos_d;            // 2 cos(w / sr) for the three-term recurrence, or 0: rotate (very low frequencies)
-    double chunk_cos, chunk_sin; // cos / sin of a chunk's advance, 1024 frames of w / sr (the angle reduced on the host)
-    int64_t start;
-    double *state_backup;        // receives the carried state on entry (a look-ahead window's snapshot), or nullptr
-};
-constexpr int kRunChunk = 64 * kBqT;     // 1024 frames: a wave's step
-constexpr int kRunBlock = 256;           // four independent waves per workgroup (they share only rows_lds)
-#ifndef PGX_SB_RUNS_WAVES
-#define PGX_SB_RUNS_WAVES 4              // waves per SIMD k_biquad_sine_runs is compiled for
-#endif
-
-// the 16 frames of a lane from the (sin, cos) of its first one, as k_biquad_settled<.., SINE>'s request() makes them
-__device__ __forceinline__ void runs_sine16(const SbRuns &sine, double sn, double cs, float (&x)[kBqT]) {
-    if (PGX_HOT(sine.two_cos_d != 0.0)) {
-        double s0 = sn, s1 = __builtin_fma(cs, sine.sin_d, sn * sine.cos_d);
-        if (PGX_HOT(sine.amp == 1.0)) {
-            x[0] = (float)s0;
-            x[1] = (float)s1;
-#pragma unroll
-            for (int j = 2; j < kBqT; ++j) {
-                const double s2 = __builtin_fma(sine.two_cos_d, s1, -s0);
-                x[j] = (float)s2;
-                s0 = s1;
-                s1 = s2;
-            }
-            return;
-        }
-        x[0] = (float)(sine.amp * s0);
-        x[1] = (float)(sine.amp * s1);
-#pragma unroll
-        for (int j = 2; j < kBqT; ++j) {
-            const double s2 = __builtin_fma(sine.two_cos_d, s1, -s0);
-            x[j] = (float)(sine.amp * s2);
-            s0 = s1;
-            s1 = s2;
-        }
-        return;
-    }
-#pragma unroll
-    for (int j = 0; j < kBqT; ++j) {
-        x[j] = (float)(sine.amp * sn);
-        const double s2 = __builtin_fma(cs, sine.sin_d, sn * sine.cos_d);
-        cs = __builtin_fma(-sn, sine.sin_d, cs * sine.cos_d);
-        sn = s2;
-    }
-}
-
-__device__ __forceinline__ double readlane63_f64(double v) {
-    const int lo = __builtin_amdgcn_readlane(__double2loint(v), 63);
-    const int hi = __builtin_amdgcn_readlane(__double2hiint(v), 63);
-    return __hiloint2double(hi, lo);
-}
-
-// Experiment switches of the window kernel (PGX_EXTRA_FLAGS; tools/c2_window_phases.py builds and times them):
-//   PGX_SB_RUNS_NO_STORE  the hot path's global stores compiled out: wrong output, the timing of everything else
-//   PGX_SB_RUNS_STAMPS    every wave records wall_clock64() (100 MHz) at entry, with its constants ready, after its
-//                         first stored chunk and at exit (pgx_biquad_sine_runs_stamps reads them)
-//   PGX_SB_RUNS_PACE_SHIFT=k  the pacing thresholds at -1, +1 and +3 times tau / 2^k instead of tau / 4
-#ifndef PGX_SB_RUNS_PACE_SHIFT
-#define PGX_SB_RUNS_PACE_SHIFT 2
-#endif
-typedef unsigned int runs_v4u __attribute__((ext_vector_type(4)));
-
-// stage_store for the runs kernel's full, aligned chunks: 16 consecutive frames per lane -> four coalesced 1 KB rows,
-// stored write-through (sc1).  A plain store leaves its line dirty in the XCD's L2, and a kernel that ends with up to
-// 32 MiB of dirty lines pays for their write-back at the boundary to the next launch: 3.5 us from the last wave's exit
-// to the next window's first entry, 1.2 us with write-through.  A run is 4 KB x `run` chunks, a block
-// 12.6 M frames and more -- far beyond the 32 MiB of L2 -- so no reader of these lines is served from L2 today and
-// nothing is lost when the store drops them.  The buffer resource is based at the chunk (the same address in every
-// lane), so every offset is below 4 KB whatever the size of the window.
-__device__ __forceinline__ void runs_store_chunk(float *lds, float *dst, int lane, const float (&y)[kBqT]) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-        *reinterpret_cast<float4 *>(lds + lane * 20 + 4 * i) = make_float4(y[4 * i], y[4 * i + 1], y[4 * i + 2], y[4 * i + 3]);
-    const uint64_t p = (uint64_t)dst;
-    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)p), hi = __builtin_amdgcn_readfirstlane((uint32_t)(p >> 32));
-    __amdgpu_buffer_rsrc_t rsrc =
-        __builtin_amdgcn_make_buffer_rsrc((void *)(((uint64_t)hi << 32) | lo), 0, kRunChunk * 4, 0x00020000);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const runs_v4u r = *reinterpret_cast<const runs_v4u *>(lds + stage_slot(i, lane));
-#ifdef PGX_SB_RUNS_NO_STORE
-        asm volatile("" ::"v"(r));
-#else
-        __builtin_amdgcn_raw_buffer_store_b128(r, rsrc, lane * 16, i * 1024, 16 /* sc1 */);
-#endif
-    }
-}
-
-// Deadline pacing.  The SIMD issues by priority, then by age, so four resident waves of equal priority do not share it:
-// the first dispatched runs at the speed of its own dependent chains, the others in the gaps it leaves, the grid leaves
-// in four steps and the last quarter of a window's bytes is written by SIMDs that hold one or two latency-bound waves
-// (DESIGN section 7).  A paced wave reads the 100 MHz wall clock at entry and once per chunk and sets its issue priority
-// by how far it is behind `done x tau`, tau being the time per chunk the launch was given: ahead of schedule 0, on it 1,
-// behind 2, behind by most of a chunk 3.  The waves of a SIMD then advance together and end together.  A priority
-// changes no sample and makes no wave wait for another; who renders which chunk stays as it is.
-//
-// tau comes from the window before, on the device: at exit one wave in kPaceRecordEvery records (launch id << 32) | its ticks
-// since entry into words[0] by atomicMax -- a newer launch's value dominates any older one, so nothing is zeroed
-// between launches -- and the next launch reads the word in its prologue.  It takes it only under the id the host names
-// as the previous runs-launch of the same plan; then tau = ticks x per_chunk (factor / (run + warm)), otherwise 0: no
-// pacing, no clock read in the chunk loop and no change of priority.  Wave 0 leaves (id << 32) | tau in words[1] for
-// pgx_biquad_sine_pacing_info.  words == nullptr (pacing switched off): the kernel reads no clock at all.
-constexpr int kPaceRecordEvery = 61;     // a prime: the recording waves fall on every SIMD, CU and quarter of the dispatch
-struct RunsPace {
-    unsigned long long *words;
-    unsigned id, prev_id;
-    float per_chunk;
-};
-
-// lag: ticks behind schedule, tau: ticks per chunk; thresholds at -1/4, +1/4 and +3/4 tau.  The pacing state lives in
-// vector registers (the kernel has none of the scalar ones to spare) with the same value in every lane; the level goes
-// through readfirstlane, so the branches are scalar ones around an s_setprio each (it takes an immediate)
-__device__ __forceinline__ void runs_pace_priority(int lag, int tau) {
-    const int q = tau >> PGX_SB_RUNS_PACE_SHIFT;
-    switch (__builtin_amdgcn_readfirstlane((lag >= -q) + (lag >= q) + (lag >= 3 * q))) {
-    case 0: __builtin_amdgcn_s_setprio(0); break;
-    case 1: __builtin_amdgcn_s_setprio(1); break;
-    case 2: __builtin_amdgcn_s_setprio(2); break;
-    default: __builtin_amdgcn_s_setprio(3); break;
-    }
-}
-
-#ifdef PGX_SB_RUNS_STAMPS
-constexpr int kRunStampWaves = 4096;
-__device__ unsigned long long g_runs_stamps[2][kRunStampWaves][4];
-#endif
-
-__global__ void __launch_bounds__(kRunBlock, PGX_SB_RUNS_WAVES)
-k_biquad_sine_runs(float *__restrict__ out, int64_t n, const double *__restrict__ coef,
-                   const double *__restrict__ tables, double *state, int run, int head, int tail, int warm, int waves,
-                   SbRuns sine, RunsPace pace
-#ifdef PGX_SB_RUNS_STAMPS
-                   , int stamp_slot
-#endif
-                   ) {
-    __shared__ __attribute__((aligned(16))) float stage_lds[(kRunBlock / 64) * kStageWords];
-    __shared__ __attribute__((aligned(16))) double rows_lds[2 * kBqT];
-#ifdef PGX_SB_RUNS_STAMPS
-    unsigned long long stamp[4] = {(unsigned long long)wall_clock64(), 0, 0, 0};
-#endif
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const double *tb = tables;
-    // the first rows of A^j (pass 2), read as LDS broadcasts (see k_biquad_settled): the kernel's only barrier
-    if (tid < 2 * kBqT) rows_lds[tid] = tb[kBqRowsAt + tid];
-    __syncthreads();
-    const int g = blockIdx.x * (kRunBlock / 64) + wave;
-    if (g >= waves) return;
-    // pacing: the entry clock, and the previous window's word on its way together with the table loads below
-    unsigned pace_t0 = 0;
-    unsigned long long pace_prev = 0;
-    if (pace.words) {
-        pace_t0 = (unsigned)wall_clock64();
-        if (pace.prev_id) pace_prev = __hip_atomic_load(pace.words, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    asm volatile("" : "+v"(pace_t0));                          // kept in a vector register, as all pacing state is
-
-    float *wlds = stage_lds + wave * kStageWords;
-    const bool io_aligned = aligned16(out);
-    const int64_t chunks = (n + kRunChunk - 1) / kRunChunk;
-    int64_t tail_start = chunks - tail;
-    if (tail_start < head) tail_start = head;
-
-    const double b0 = coef[0], b1 = coef[1], b2 = coef[2], a1 = coef[3], a2 = coef[4];
-    M2 pstep[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) pstep[k] = load_m2(tb + 4 * k);
-    const M2 pwave = load_m2(tb + 24);
-    const M2 mlane = load_m2(tb + 28 + 4 * lane);
-    const M2 m16 = load_m2(tb + 28 + 4 * ((lane & 15) + 1));
-    const M2 m32 = load_m2(tb + 28 + 4 * ((lane & 31) + 1));
-#ifdef PGX_SB_RUNS_STAMPS
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::"v"(mlane.a), "v"(m16.a), "v"(m32.a), "v"(pwave.a), "v"(b0) : "memory");
-    stamp[1] = wall_clock64();
-#endif
-    // ticks per chunk, or 0: not paced (no history under the id the host expects).  Below 2^24, 0.17 s per chunk
-    int pace_tau = 0;
-    if (pace.prev_id && (unsigned)(pace_prev >> 32) == pace.prev_id)
-        pace_tau = (int)fminf((float)(unsigned)pace_prev * pace.per_chunk, 16777216.0f);
-    unsigned pace_due = pace_t0;                               // the clock at which the current chunk is due to begin
-    asm volatile("" : "+v"(pace_tau), "+v"(pace_due));
-
-    // renders the chunks [cb, ce) after `warm` chunks of warm-up (from the carried state at chunk 0).  Called once per
-    // range, not from a loop over the ranges: the sine's constants are then not hoisted into registers for all of it
-    auto render = [&](const int64_t cb, const int64_t ce) {
-        int64_t c = cb == 0 ? 0 : cb - warm;
-        V2 carry{0.0, 0.0};
-        if (cb == 0) {
-            carry = V2{state[0], state[1]};
-            if (sine.state_backup && lane == 0) {              // wave 0 alone reads and writes the state
-                sine.state_backup[0] = carry.x;
-                sine.state_backup[1] = carry.y;
-            }
-        }
-        // the lane's first frame: k_sine's evaluation for the first chunk, then turned by a chunk's advance
-        double sn, cs;
-        {
-            const double t = pgx::pgx_div_by((double)(sine.start + c * kRunChunk + lane * kBqT), sine.sr, sine.inv_sr);
-            pgx::pgx_sincos_bounded(sine.phase0 + sine.w * t, sn, cs);
-        }
-#pragma nounroll
-        for (; c < ce; ++c) {
-            // the clock is read here, where no LDS access is outstanding: it returns on the counter LDS reads return
-            // on, and a wait for it further down would hold the pass-2 row reads back
-            if (__builtin_amdgcn_readfirstlane(pace_tau)) {
-                runs_pace_priority((int)((unsigned)wall_clock64() - pace_due), pace_tau);
-                pace_due += (unsigned)pace_tau;
-            }
-            float xf[kBqT];
-            runs_sine16(sine, sn, cs, xf);
-            // zero-state response of the lane's 16 frames
-            V2 e{0.0, 0.0};
-            const double na1 = -a1, na2 = -a2;
-            double yz[kBqT];
-#pragma unroll
-            for (int j = 0; j < kBqT; ++j) {
-                const double x = (double)xf[j];
-                const double y = __builtin_fma(b0, x, e.x);
-                e.x = __builtin_fma(na1, y, __builtin_fma(b1, x, e.y));
-                e.y = __builtin_fma(na2, y, b2 * x);
-                yz[j] = y;
-            }
-            // inclusive scan over the wave (k_biquad_settled's)
-            e = mv_add_fma(pstep[0], dpp_v2<0x111, 0xf>(e), e);
-            e = mv_add_fma(pstep[1], dpp_v2<0x112, 0xf>(e), e);
-            e = mv_add_fma(pstep[2], dpp_v2<0x114, 0xf>(e), e);
-            e = mv_add_fma(pstep[3], dpp_v2<0x118, 0xf>(e), e);
-            e = mv_add_fma(m16, dpp_v2<0x142, 0xa>(e), e);
-            e = mv_add_fma(m32, dpp_v2<0x143, 0xc>(e), e);
-
-            const int64_t w0 = c * kRunChunk;
-            if (PGX_HOT(c >= cb)) {
-                const int64_t f0 = w0 + lane * kBqT;
-                const V2 ex = dpp_v2<0x138, 0xf>(e);           // previous lane's inclusive value, 0 for lane 0
-                const V2 zin = mv_add_fma(mlane, carry, ex);
-                float yf[kBqT];
-                const double *rows = rows_lds;
-#pragma unroll
-                for (int j = 0; j < kBqT; ++j)
-                    yf[j] = (float)__builtin_fma(rows[2 * j], zin.x, __builtin_fma(rows[2 * j + 1], zin.y, yz[j]));
-                if (PGX_HOT(io_aligned && w0 + kRunChunk <= n))
-                    runs_store_chunk(wlds, out + w0, lane, yf);
-                else
-                    store_frames<kBqT>(out, f0, n, 1, 0, yf);
-#ifdef PGX_SB_RUNS_STAMPS
-                if (!stamp[2]) {
-                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                    stamp[2] = wall_clock64();
-                }
-#endif
-                if (PGX_COLD(f0 <= n - 1 && n - 1 - f0 < kBqT)) {  // the lane holding the last frame: new state
-                    // its frames made again (bit for bit the same), rather than kept in 16 registers for this branch
-                    double rs = sn, rc = cs;
-                    asm volatile("" : "+v"(rs), "+v"(rc));
-                    runs_sine16(sine, rs, rc, xf);
-                    V2 z = zin;
-                    for (int j = 0; j <= (int)(n - 1 - f0); ++j) {
-                        double x = (double)xf[j];
-                        double y = z.x + b0 * x;
-                        double z0 = (z.y + b1 * x) - a1 * y;
-                        z.y = b2 * x - a2 * y;
-                        z.x = z0;
-                    }
-                    state[0] = z.x;
-                    state[1] = z.y;
-                }
-            }
-            // the wave's state after this chunk: what the state in front of it leaves, plus lane 63's inclusive value
-            carry = mv_add_fma(pwave, carry, V2{readlane63_f64(e.x), readlane63_f64(e.y)});
-            const double s2 = __builtin_fma(sn, sine.chunk_cos, cs * sine.chunk_sin);
-            cs = __builtin_fma(cs, sine.chunk_cos, -(sn * sine.chunk_sin));
-            sn = s2;
-        }
-    };
-    // the chunks of this wave, and for wave 0 the tail
-    // (two copies of the loop, not three: each keeps its xf[] in registers only while the three do not outgrow the
-    // compiler's budget for such arrays, and with the pacing code in the loop a third copy's went to scratch)
-    {
-        const int64_t cb = g == 0 ? 0 : head + (int64_t)(g - 1) * run;
-        const int64_t ce = g == 0 ? (head < chunks ? head : chunks) : (cb + run < tail_start ? cb + run : tail_start);
-        render(cb, ce);
-        if (g == 0) render(tail_start, chunks);
-    }
-#ifdef PGX_SB_RUNS_STAMPS
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    stamp[3] = wall_clock64();
-    if (lane == 0 && g < kRunStampWaves)
-        for (int k = 0; k < 4; ++k) g_runs_stamps[stamp_slot & 1][g][k] = stamp[k];
-#endif
-    // this wave's ticks for the next window's tau: fire and forget, nothing waits for the atomic.  One wave in
-    // kPaceRecordEvery records: atomics on one address are served one after the other, about 11 ns each, and with every
-    // wave of a 16 M-frame window recording the kernel ended 36 us later (52.8 us against 16.2 us)
-    if (pace.words && g % kPaceRecordEvery == 0) {
-        const unsigned long long ticks = (unsigned)wall_clock64() - pace_t0;
-        if (lane == 0) {
-            atomicMax(pace.words, ((unsigned long long)pace.id << 32) | ticks);
-            if (g == 0) pace.words[1] = ((unsigned long long)pace.id << 32) | (unsigned)pace_tau;
-        }
-    }
-}
-
-struct BqPlan {
-    int seg_tiles;
-    int nseg;
-};
-
-struct BqSettledPlan {
-    bool ok;
-    int seg, head, tail, warm, groups;        // in 4096-frame halves
-};
-
-BqSettledPlan biquad_settled_plan(int batch, int64_t n, int channels, int64_t settle_frames, bool have_tables,
-                                  int workgroups = 512) {
-    BqSettledPlan p{};
-    if (!have_tables) return p;
-    const int64_t halves = pgx::ceil_div(n, kSbHalf);
-    const int64_t chains = (int64_t)batch * channels;
-    const int64_t warm = pgx::ceil_div(settle_frames, kSbHalf);
-    if (settle_frames > 0 && warm <= kSbMaxWarm) {
-        int64_t want = workgroups / chains;                    // 512: two resident workgroups per CU, one round
-        if (want < 1) want = 1;
-        int64_t seg = pgx::ceil_div(halves, want);
-        if (seg < warm) seg = warm;                            // warm-up never exceeds the rendered part
-        const int64_t head = seg / 2 > warm ? seg / 2 : warm;  // workgroup 0: head + tail ~ one segment
-        const int64_t tail = seg - head > 1 ? seg - head : 1;
-        if (halves > head + tail) {
-            p.ok = true;
-            p.seg = (int)seg;
-            p.head = (int)head;
-            p.tail = (int)tail;
-            p.warm = (int)warm;
-            p.groups = 1 + (int)pgx::ceil_div(halves - head - tail, seg);
-            return p;
-        }
-    }
-    // One workgroup per chain over the whole block: nothing is assumed (the carried state is read, no
-    // warm-up), this is just the faster tile engine.  Worth it when the chains alone fill the machine
-    // (voice banks) or the block is a tile or two; long lone chains keep the segment-parallel exact pair.
-    if (chains >= 64 || halves <= 2) {
-        p.ok = true;
-        p.seg = (int)halves;
-        p.head = (int)halves;
-        p.tail = 0;
-        p.warm = 0;
-        p.groups = 1;
-    }
-    return p;
-}
-
-BqPlan biquad_plan(int batch, int64_t n, int channels) {
-    int64_t tiles = pgx::ceil_div(n, kBqTile);
-    int64_t chains = (int64_t)batch * channels;
-    int64_t want = 512 / chains;                  // aim for ~512 workgroups (2 per CU) in flight
-    if (want < 1) want = 1;
-    if (want > kBqMaxSeg) want = kBqMaxSeg;
-    if (want > tiles) want = tiles;
-    BqPlan p;
-    p.seg_tiles = (int)pgx::ceil_div(tiles, want);
-    p.nseg = (int)pgx::ceil_div(tiles, p.seg_tiles);
-    return p;
-}
 
 // ================================================================================================
 // BlitSawPE
 // ================================================================================================
 constexpr int kSawT = 8;
 constexpr int kSawTile = kBlock * kSawT;   // 2048 frames
-constexpr double kPi = 3.141592653589793;
 
 constexpr int kSawWideWaves = 8;                  // 512-thread form for a handful of oscillators (203 VGPRs: 2 waves per SIMD)
 struct SawShared {
@@ -3179,162 +1899,6 @@ SawPlan saw_plan(int batch, int64_t n, bool streams) {
 }
 
 // ================================================================================================
-// SinePE, stateful path
-// ================================================================================================
-constexpr int kSinT = 8;
-constexpr int kSinTile = kBlock * kSinT;
-
-// One tile of the stateful sine: frames [base, base + kSinTile) of a row of n.  The thread's increments are summed serially
-// over its kSinT frames, block_excl_sum gives its offset inside the tile and the tile's total (which depends on no carry);
-// the phase of a frame is ((carry_sum + off) + loc) + initial.  TOTAL_ONLY: the total alone, nothing else read or written
-// -- what the time-parallel bank's first launch needs; the same code, so the same sum.  k_sine_stateful and the bank
-// kernels all come through here: their samples are the same by construction (-ffp-contract=off: inlining changes no sum).
-template <bool TOTAL_ONLY>
-__device__ __forceinline__ double sine_tile(float *out, int64_t base, int64_t n, int channels, double sr,
-                                            const pgx_sine_stateful_params &p, const float *freq, const float *amp,
-                                            const float *phase_mod, double carry_sum, double initial, double *lds,
-                                            double &final_phase, bool &have_final) {
-    const double two_pi = 2.0 * kPi;
-    const int64_t f0 = base + (int64_t)threadIdx.x * kSinT;
-    double loc[kSinT];
-    double run = 0.0;
-    // the control values of the thread's frames first, unconditionally (clamped index): behind the bounds test every
-    // load is waited for at once, one memory latency per value on a kernel that is one workgroup walking the block
-    float f_in[kSinT], pm_in[kSinT], a_in[kSinT];
-    if (freq) {
-#pragma unroll
-        for (int j = 0; j < kSinT; ++j) f_in[j] = freq[(f0 + j < n) ? f0 + j : n - 1];
-    }
-    if (!TOTAL_ONLY && phase_mod) {
-#pragma unroll
-        for (int j = 0; j < kSinT; ++j) pm_in[j] = phase_mod[(f0 + j < n) ? f0 + j : n - 1];
-    }
-    if (!TOTAL_ONLY && amp) {
-#pragma unroll
-        for (int j = 0; j < kSinT; ++j) a_in[j] = amp[(f0 + j < n) ? f0 + j : n - 1];
-    }
-#pragma unroll
-    for (int j = 0; j < kSinT; ++j) {
-        double f = p.freq;
-        if (freq) f = (f0 + j < n) ? (double)f_in[j] : 0.0;
-        double inc = (f0 + j < n) ? (two_pi * f) / sr : 0.0;
-        run = run + inc;
-        loc[j] = run;
-    }
-    double tile_total;
-    double off = block_excl_sum(run, lds, tile_total);
-    if (TOTAL_ONLY) return tile_total;
-    const double chunk_base = carry_sum + off;
-
-    float yf[kSinT];
-#pragma unroll
-    for (int j = 0; j < kSinT; ++j) {
-        double ph = (chunk_base + loc[j]) + initial;             // cumsum + initial_phase (:217)
-        double pm = p.phase;
-        if (phase_mod) pm = (f0 + j < n) ? (double)pm_in[j] : 0.0;
-        ph = ph + pm;                                            // + phase_mod (:220-223)
-        double a = p.amp;
-        if (amp) a = (f0 + j < n) ? (double)a_in[j] : 0.0;
-        yf[j] = (float)(a * pgx::pgx_sin(ph));
-        if (f0 + j == n - 1) {
-            final_phase = ph;
-            have_final = true;
-        }
-    }
-    store_frames_tiled<kSinT>(out, f0, n, channels, yf);
-    return tile_total;
-}
-
-// One workgroup walks a row tile by tile; the carry is the left fold of the tiles' totals, ((0 + T0) + T1) + ...
-__device__ __forceinline__ void sine_walk(float *out, int64_t n, int channels, double sr,
-                                          const pgx_sine_stateful_params &p, const float *freq, const float *amp,
-                                          const float *phase_mod, double *state, double *lds) {
-    // sine_pe.py:203-214: first render starts from the scalar phase (0 when phase is a PE)
-    const bool inited = state[1] != 0.0;
-    const double initial = inited ? state[0] : (p.phase_is_stream ? 0.0 : p.phase);
-    double carry_sum = 0.0;
-    double final_phase = 0.0;
-    bool have_final = false;
-    for (int64_t base = 0; base < n; base += kSinTile)
-        carry_sum = carry_sum + sine_tile<false>(out, base, n, channels, sr, p, freq, amp, phase_mod, carry_sum, initial,
-                                                 lds, final_phase, have_final);
-    if (have_final) {
-        state[0] = final_phase;
-        state[1] = 1.0;
-    }
-}
-
-__global__ void __launch_bounds__(kBlock)
-k_sine_stateful(float *out, int64_t n, int channels, double sr, const pgx_sine_stateful_params *params,
-                const float *freq, const float *amp, const float *phase_mod, double *state) {
-    __shared__ double lds[kWaves];
-    const pgx_sine_stateful_params p = params[0];
-    sine_walk(out, n, channels, sr, p, freq, amp, phase_mod, state, lds);
-}
-
-// Bank of stateful sines (pgx_sine_stateful_bank, voice_bank.py), the walk: k_sine_stateful with the voice in blockIdx.x.
-__global__ void __launch_bounds__(kBlock)
-k_sine_stateful_bank(float *out, int64_t out_stride, int64_t n, int channels, double sr,
-                     const pgx_sine_stateful_params *params, const float *freq, int64_t freq_stride, const float *amp,
-                     int64_t amp_stride, const float *phase_mod, int64_t phase_stride, double *state) {
-    __shared__ double lds[kWaves];
-    const int64_t v = blockIdx.x;
-    const pgx_sine_stateful_params p = params[v];
-    sine_walk(out + v * out_stride, n, channels, sr, p, freq ? freq + v * freq_stride : nullptr,
-              amp ? amp + v * amp_stride : nullptr, phase_mod ? phase_mod + v * phase_stride : nullptr, state + v * 2, lds);
-}
-
-// The time-parallel form: a workgroup per tile and voice, two launches, nothing passes between the workgroups of a launch.
-// Voice v's slice of the workspace: {phase, initialised} as they were on entry, then one total per tile.
-//   k_sine_bank_totals  tile t's total, exactly as the walk sums it; tile 0's workgroup copies state[v] (the apply launch
-//                       overwrites state[v] while others of its workgroups, not resident yet, still need what was there).
-//   k_sine_bank_apply   carry = ((0 + T0) + T1) + ... + T(t-1), folded serially in the walk's order (a sum of group sums
-//                       is another association); the tile's frames; the owner of frame n - 1 writes state[v].
-__global__ void __launch_bounds__(kBlock)
-k_sine_bank_totals(int64_t n, double sr, const pgx_sine_stateful_params *params, const float *freq, int64_t freq_stride,
-                   const double *state, double *ws, int64_t tiles) {
-    __shared__ double lds[kWaves];
-    const int64_t t = blockIdx.x, v = blockIdx.y;
-    const pgx_sine_stateful_params p = params[v];
-    double *slice = ws + v * (tiles + 2);
-    double final_phase = 0.0;
-    bool have_final = false;
-    const double total = sine_tile<true>(nullptr, t * kSinTile, n, 1, sr, p, freq ? freq + v * freq_stride : nullptr,
-                                         nullptr, nullptr, 0.0, 0.0, lds, final_phase, have_final);
-    if (threadIdx.x == 0) {
-        slice[2 + t] = total;
-        if (t == 0) {
-            slice[0] = state[v * 2 + 0];
-            slice[1] = state[v * 2 + 1];
-        }
-    }
-}
-
-__global__ void __launch_bounds__(kBlock)
-k_sine_bank_apply(float *out, int64_t out_stride, int64_t n, int channels, double sr,
-                  const pgx_sine_stateful_params *params, const float *freq, int64_t freq_stride, const float *amp,
-                  int64_t amp_stride, const float *phase_mod, int64_t phase_stride, double *state, const double *ws,
-                  int64_t tiles) {
-    __shared__ double lds[kWaves];
-    const int64_t t = blockIdx.x, v = blockIdx.y;
-    const pgx_sine_stateful_params p = params[v];
-    const double *slice = ws + v * (tiles + 2);
-    const bool inited = slice[1] != 0.0;                         // (never state[v]: see above)
-    const double initial = inited ? slice[0] : (p.phase_is_stream ? 0.0 : p.phase);
-    double carry_sum = 0.0;
-    for (int64_t i = 0; i < t; ++i) carry_sum = carry_sum + slice[2 + i];
-    double final_phase = 0.0;
-    bool have_final = false;
-    sine_tile<false>(out + v * out_stride, t * kSinTile, n, channels, sr, p, freq ? freq + v * freq_stride : nullptr,
-                     amp ? amp + v * amp_stride : nullptr, phase_mod ? phase_mod + v * phase_stride : nullptr, carry_sum,
-                     initial, lds, final_phase, have_final);
-    if (have_final) {
-        state[v * 2 + 0] = final_phase;
-        state[v * 2 + 1] = 1.0;
-    }
-}
-
-// ================================================================================================
 // BiquadPE, time-varying coefficients
 // ================================================================================================
 constexpr int kBvT = 4;
@@ -3742,63 +2306,6 @@ k_biquad_varying_bank(float *out, int64_t out_stride, const float *in, int64_t i
 }
 
 // ================================================================================================
-// PeriodicGate with PE-driven frequency / duty / phase: FunctionGenPE's stateful rectangle path
-// (function_gen_pe.py:157-193): base = mod(phase0 + [0, cumsum(f/sr)[:-1]], 1); gate = mod(base + ph, 1) < duty.
-// One workgroup: exclusive prefix sum of the increments, like the stateful sine.
-// state = { carried phase }.
-// ================================================================================================
-constexpr int kGateT = 8;
-constexpr int kGateTile = kBlock * kGateT;
-
-__global__ void __launch_bounds__(kBlock)
-k_gate_stateful(float *out, int64_t n, double sr, double freq_scalar, double duty_scalar, double phase_scalar,
-                const float *freq, const float *duty, const float *phase, double *state) {
-    __shared__ double lds[kWaves];
-    const int tid = threadIdx.x;
-    const double phase0 = state[0];
-    double carry_sum = 0.0;
-    for (int64_t base = 0; base < n; base += kGateTile) {
-        const int64_t f0 = base + (int64_t)tid * kGateT;
-        double loc[kGateT];
-        double run = 0.0;
-        // control values first, unconditionally (see k_sine_stateful)
-        float f_in[kGateT], ph_in[kGateT], d_in[kGateT];
-        if (freq) {
-#pragma unroll
-            for (int j = 0; j < kGateT; ++j) f_in[j] = freq[(f0 + j < n) ? f0 + j : n - 1];
-        }
-        if (phase) {
-#pragma unroll
-            for (int j = 0; j < kGateT; ++j) ph_in[j] = phase[(f0 + j < n) ? f0 + j : n - 1];
-        }
-        if (duty) {
-#pragma unroll
-            for (int j = 0; j < kGateT; ++j) d_in[j] = duty[(f0 + j < n) ? f0 + j : n - 1];
-        }
-#pragma unroll
-        for (int j = 0; j < kGateT; ++j) {
-            loc[j] = run;                                             // exclusive within the chunk
-            const double f = freq ? ((f0 + j < n) ? (double)f_in[j] : 0.0) : freq_scalar;
-            run = run + ((f0 + j < n) ? f / sr : 0.0);
-        }
-        double tile_total;
-        const double off = block_excl_sum(run, lds, tile_total);
-        const double chunk_base = carry_sum + off;
-        carry_sum = carry_sum + tile_total;
-#pragma unroll
-        for (int j = 0; j < kGateT; ++j) {
-            if (f0 + j >= n) break;
-            const double b = pgx::pgx_mod1(phase0 + (chunk_base + loc[j]));
-            const double ph = pgx::pgx_mod1(b + (phase ? (double)ph_in[j] : phase_scalar));
-            double d = duty ? (double)d_in[j] : duty_scalar;
-            d = d < 0.0 ? 0.0 : (d > 1.0 ? 1.0 : d);
-            out[f0 + j] = (ph < d) ? 1.0f : 0.0f;
-        }
-    }
-    if (tid == 0) state[0] = pgx::pgx_mod1(phase0 + carry_sum);       // mod(phase + sum(dt), 1)
-}
-
-// ================================================================================================
 // SVFilterPE (svfilter_pe.py:41-205, 404-500): trapezoidal state variable filter,
 //   out = c0*x + c1*s0 + c2*s1;   s' = B*x + A*s   with a full (possibly per-sample) 2x2 A.
 // One workgroup per channel chain, time-varying 2x2 affine scan like the varying biquad.
@@ -4089,852 +2596,10 @@ k_svf_bank(float *out, int64_t out_stride, const float *in, int64_t in_stride, i
     }
 }
 
-// ================================================================================================
-// EnvelopePE (envelope_pe.py:128-271)
-// ================================================================================================
-// Detector: |x| (peak) or the block-local centred running RMS of scipy.ndimage.uniform_filter1d(x^2,
-// size=window, mode='nearest') (envelope_pe.py:208-225).  Output float64 (frames, channels).
-// RMS sums each window as head + whole 64-frame blocks + tail (k_env_blocks holds the block sums of squares),
-// with the 'nearest' edge samples weighted by how often the clamped window repeats them.
-constexpr int kEnvBlock = 64;
-
-__global__ void __launch_bounds__(kBlock)
-k_env_blocks(double *blocks, const float *in, int64_t n, int channels) {
-    const int lane = threadIdx.x & 63;
-    const int64_t nblk = (n + kEnvBlock - 1) / kEnvBlock;
-    const int64_t item = (int64_t)blockIdx.x * kWaves + (threadIdx.x >> 6);          // one wave per (block, channel)
-    if (item >= nblk * channels) return;
-    const int64_t b = item / channels;
-    const int c = (int)(item - b * channels);
-    const int64_t f = b * kEnvBlock + lane;
-    double v = 0.0;
-    if (f < n) {
-        v = (double)in[f * channels + c];
-        v = v * v;
-    }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v = v + __shfl_down(v, d, 64);
-    if (lane == 0) blocks[item] = v;
-}
-
-__global__ void __launch_bounds__(kBlock)
-k_env_detect(double *det, const float *in, const double *blocks, int64_t n, int channels, int rms_window,
-             int64_t period) {
-    const int64_t total = n * channels;
-    const int64_t stride = (int64_t)gridDim.x * kBlock;
-    auto sq = [&](int64_t f, int c) {
-        const double v = (double)in[f * channels + c];
-        return v * v;
-    };
-    for (int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x; e < total; e += stride) {
-        const int64_t i = e / channels;
-        const int c = (int)(e - i * channels);
-        if (rms_window <= 0) {
-            det[e] = fabs((double)in[e]);
-            continue;
-        }
-        // window [i - size/2, i - size/2 + size) with indices clamped to the block ('nearest').  The block is the
-        // caller's: when a look-ahead window renders several of the caller's blocks at once (`period` frames each)
-        // the detector restarts at every one of their edges, as the reference's per-block filter does
-        int64_t p0 = 0, p1 = n;
-        if (period > 0) {
-            p0 = (i / period) * period;
-            p1 = p0 + period < n ? p0 + period : n;
-        }
-        int64_t lo = i - rms_window / 2, hi = lo + rms_window;
-        double acc = 0.0;
-        if (lo < p0) {
-            acc = acc + (double)(p0 - lo) * sq(p0, c);
-            lo = p0;
-        }
-        if (hi > p1) {
-            acc = acc + (double)(hi - p1) * sq(p1 - 1, c);
-            hi = p1;
-        }
-        const int64_t b0 = (lo + kEnvBlock - 1) / kEnvBlock, b1 = hi / kEnvBlock;        // whole blocks [b0, b1)
-        if (b0 < b1) {
-            for (int64_t f = lo; f < b0 * kEnvBlock; ++f) acc = acc + sq(f, c);
-            for (int64_t b = b0; b < b1; ++b) acc = acc + blocks[b * channels + c];
-            for (int64_t f = b1 * kEnvBlock; f < hi; ++f) acc = acc + sq(f, c);
-        } else {
-            for (int64_t f = lo; f < hi; ++f) acc = acc + sq(f, c);
-        }
-        det[e] = sqrt(acc / (double)rms_window);
-    }
-}
-
-constexpr int kEnvT = 8;
-constexpr int kEnvTile = kBlock * kEnvT;
-
-// attack == release (envelope_pe.py:167-180): one-pole lfilter  y = z + c*x;  z = (1-c)*y.
-__global__ void __launch_bounds__(kBlock)
-k_env_onepole(float *out, const double *det, int64_t n, int channels, double coeff, double *state) {
-    __shared__ double lds[kWaves];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int ch = blockIdx.x;
-    const double lam = 1.0 - coeff;
-    double lamp[6], lam_wave, lam_lane = 1.0;
-    {
-        double l = lam;
-#pragma unroll
-        for (int s = 1; s < kEnvT; s <<= 1) l = l * l;
-#pragma unroll
-        for (int k = 0; k < 6; ++k) {
-            lamp[k] = l;
-            if (lane & (1 << k)) lam_lane = lam_lane * l;
-            l = l * l;
-        }
-        lam_wave = l;
-    }
-    double carry = state[ch];
-    double final_y = 0.0;
-    bool have_final = false;
-    for (int64_t base = 0; base < n; base += kEnvTile) {
-        const int64_t f0 = base + (int64_t)tid * kEnvT;
-        double xs[kEnvT];
-        double e = 0.0;
-#pragma unroll
-        for (int j = 0; j < kEnvT; ++j) {
-            xs[j] = (f0 + j < n) ? det[(f0 + j) * channels + ch] : 0.0;
-            // dead samples must act as the identity map, so the zero-state response only folds live ones
-            if (f0 + j < n) e = lam * e + coeff * xs[j];
-            else e = lam * e;
-        }
-        double y = block_scan_scalar_affine(e, lamp, lam_wave, lam_lane, lds, carry);
-        float yf[kEnvT];
-#pragma unroll
-        for (int j = 0; j < kEnvT; ++j) {
-            const double z = lam * y;
-            const double yn = z + coeff * xs[j];
-            yf[j] = (float)yn;
-            if (f0 + j < n) y = yn;
-            if (f0 + j == n - 1) {
-                final_y = yn;
-                have_final = true;
-            }
-        }
-        store_frames<kEnvT>(out, f0, n, channels, ch, yf);
-    }
-    if (have_final) state[ch] = final_y;
-}
-
-
-// attack != release (envelope_pe.py:259-271), time-parallel.  One sample's update
-//     e' = e + c(e) * (t - e),   c = attack if t > e else release
-// is a continuous, increasing, two-piece linear map of e, so a thread's T samples compose to a piecewise linear
-// map whose piece around a given entry level is found by stepping the samples literally from that level.  A
-// window of NW*64*T samples is solved by Newton's method on that piecewise linear system: every thread steps its
-// samples from its current entry level (reference arithmetic), recording the affine piece (A, B) it passed
-// through; a workgroup scan of the pieces gives every thread a new entry level; repeat until no entry level
-// moves by more than 1e-13 of itself.  Thread k's entry is final after at most k+1 rounds (it only depends on
-// threads before it), so the loop ends; in practice it takes 2..6 rounds (semismooth Newton).  The samples written
-// are literal steps from entry levels within 1e-13 of the converged ones: against the sequential reference they
-// differ by that much (float32 output resolves 6e-8).  `det` == nullptr: peak detection fused (|in|).
-constexpr double kEnvSettled = 1e-13;
-template <int NW, int T, bool PEAK>
-__global__ void __launch_bounds__(NW * 64)
-k_env_newton(float *out, const float *in, const double *det, int64_t n, int channels, double attack_coeff,
-             double release_coeff, double *state, const int *run_flag) {
-    if (run_flag != nullptr && *run_flag == 0) return;       // armed only when the all-windows form gave up
-    __shared__ double s_a[2][NW], s_b[2][NW], s_pa[T + 1], s_pr[T + 1];
-    __shared__ int s_moved[2][NW];
-    constexpr int kWindow = NW * 64 * T;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int ch = blockIdx.x;
-    double e_in = state[ch];
-    if (tid == 0) {                                   // (1-c)^k: a thread's slope is a product of these
-        double pa = 1.0, pr = 1.0;
-        for (int k = 0; k <= T; ++k) {
-            s_pa[k] = pa;
-            s_pr[k] = pr;
-            pa = pa * (1.0 - attack_coeff);
-            pr = pr * (1.0 - release_coeff);
-        }
-    }
-    __syncthreads();
-
-    // HBM is touched with lane-contiguous accesses (element i of thread tid is frame i*NW*64 + tid of the window);
-    // the rounds want T consecutive frames per thread.  Both directions go through LDS, a chunk of T frames padded
-    // to T+1 words so that neither access pattern conflicts.  (Thread-contiguous global accesses cost 8x the L1->L2
-    // requests here: 2 us per window, as much as the rounds.)
-    using Raw = typename std::conditional<PEAK, float, double>::type;
-    constexpr int kThreads = NW * 64;
-    __shared__ Raw s_x[kWindow + kWindow / T];
-    __shared__ float s_y[kWindow + kWindow / T];
-    Raw raw[T];
-    auto fetch = [&](int64_t wbase) {                 // branch-free (clamped) so that the loads pipeline
-#pragma unroll
-        for (int i = 0; i < T; ++i) {
-            int64_t f = wbase + i * kThreads + tid;
-            f = f < n ? f : n - 1;
-            if constexpr (PEAK) raw[i] = in[f * channels + ch];
-            else raw[i] = det[f * channels + ch];
-        }
-    };
-    auto stage = [&]() {
-#pragma unroll
-        for (int i = 0; i < T; ++i) {
-            const int k = i * kThreads + tid;
-            s_x[k + k / T] = raw[i];
-        }
-    };
-    double t[T];
-    auto take = [&]() {
-#pragma unroll
-        for (int j = 0; j < T; ++j) {
-            const Raw v = s_x[tid * (T + 1) + j];
-            t[j] = PEAK ? fabs((double)v) : (double)v;
-        }
-    };
-    fetch(0);
-    stage();
-    __syncthreads();
-    take();
-    for (int64_t base = 0; base < n; base += kWindow) {
-        const int64_t f0 = base + (int64_t)tid * T;
-        const int live = (n - f0 >= T) ? T : (n - f0 > 0 ? (int)(n - f0) : 0);
-        const bool has_next = base + kWindow < n;
-        const bool full = base + kWindow <= n;
-        if (has_next) fetch(base + kWindow);                               // next window, in flight
-
-        // Two barriers per round (pieces, then the "an entry level moved" flags); LDS is double-buffered by round
-        // parity so that no third one is needed.
-        double entry = e_in, exit_level = e_in;
-        double y[T];
-        for (int round = 0; round <= NW * 64 + 1; ++round) {
-            double e = entry;
-            int attacks = 0;
-            if (full) {                                  // every thread owns T live samples: no per-sample guard
-#pragma unroll
-                for (int j = 0; j < T; ++j) {
-                    const bool attack = t[j] > e;
-                    e = e + (attack ? attack_coeff : release_coeff) * (t[j] - e);
-                    attacks += attack ? 1 : 0;
-                    y[j] = e;
-                }
-            } else {
-#pragma unroll
-                for (int j = 0; j < T; ++j) {
-                    const bool on = j < live;
-                    const bool attack = t[j] > e;
-                    const double stepped = e + (attack ? attack_coeff : release_coeff) * (t[j] - e);
-                    attacks += (on && attack) ? 1 : 0;
-                    e = on ? stepped : e;
-                    y[j] = e;
-                }
-            }
-            // the affine piece this thread passed through: slope from the regime counts, offset from the exit
-            double a = s_pa[attacks] * s_pr[live - attacks];
-            double b = __builtin_fma(-a, entry, e);
-            // inclusive scan of the pieces over the wave (lanes without a source see the identity)
-#define PGX_ENV_STEP(CTRL, MASK)                                            \
-            {                                                               \
-                const double ao = dpp_f64_keep<CTRL, MASK>(1.0, a);         \
-                const double bo = dpp_f64_keep<CTRL, MASK>(0.0, b);         \
-                b = __builtin_fma(a, bo, b);                                \
-                a = a * ao;                                                 \
-            }
-            PGX_ENV_STEP(0x111, 0xf) PGX_ENV_STEP(0x112, 0xf) PGX_ENV_STEP(0x114, 0xf) PGX_ENV_STEP(0x118, 0xf)
-            PGX_ENV_STEP(0x142, 0xa) PGX_ENV_STEP(0x143, 0xc)
-#undef PGX_ENV_STEP
-            const int buf = round & 1;
-            if (lane == 63) {
-                s_a[buf][wave] = a;
-                s_b[buf][wave] = b;
-            }
-            __syncthreads();
-            double cw = e_in, cn = e_in;
-#pragma unroll
-            for (int w = 0; w < NW; ++w) {
-                const double wa = s_a[buf][w], wb = s_b[buf][w];
-                if (w < wave) cw = __builtin_fma(wa, cw, wb);
-                cn = __builtin_fma(wa, cn, wb);
-            }
-            exit_level = cn;
-            const double aex = dpp_f64_keep<0x138, 0xf>(1.0, a);            // wave_shr:1 -> exclusive
-            const double bex = dpp_f64_keep<0x138, 0xf>(0.0, b);
-            const double fresh = __builtin_fma(aex, cw, bex);
-            // settled when no entry level moves by more than rounding noise (the offsets above carry ~1e-16)
-            const bool moved = live > 0 && fabs(fresh - entry) > kEnvSettled * (fabs(fresh) + fabs(entry));
-            entry = fresh;
-            const bool wave_moved = __ballot(moved) != 0ull;
-            if (lane == 0) s_moved[buf][wave] = wave_moved ? 1 : 0;
-            __syncthreads();
-            int any = 0;
-#pragma unroll
-            for (int w = 0; w < NW; ++w) any |= s_moved[buf][w];
-            if (!any) break;
-        }
-#pragma unroll
-        for (int j = 0; j < T; ++j) s_y[tid * (T + 1) + j] = (float)y[j];
-        if (has_next) stage();
-        __syncthreads();                               // (the next writes to s_x / s_y come after the next rounds' barriers)
-#pragma unroll
-        for (int i = 0; i < T; ++i) {
-            const int k = i * kThreads + tid;
-            if (base + k < n) out[(base + k) * channels + ch] = s_y[k + k / T];
-        }
-        if (has_next) take();
-        e_in = exit_level;                           // composition of all pieces (dead samples are the identity)
-    }
-    if (tid == 0) state[ch] = e_in;
-}
-
-// The same follower over a LONG block (look-ahead windows hand it millions of frames): all 8192-sample windows
-// at once.  A window's exit level is an affine function of its entry level on the piece the trajectory runs
-// through (A = product of the per-sample slopes, tiny after thousands of samples), so the entry levels of all
-// windows solve a piecewise linear system of their own, again by Newton rounds -- one launch per round:
-//   round 0   every window is solved (the inner rounds above) from the carried level and publishes its piece;
-//   round r   a window folds the pieces of the windows before it (published in round r-1) onto the carried
-//             level; if that entry is the one its samples were rendered from (1e-13) it republishes its piece and
-//             is done, otherwise it renders again from the new entry and raises the round's "moved" flag.
-// No window moved in a round = every window was rendered from the entry the others imply: converged; later
-// launches return at once.  Window w is final after at most w+1 rounds, audio settles in 2..4 (a window forgets
-// its entry by orders of magnitude).  If kEnvMwRounds are not enough the finishing kernel arms the sequential
-// kernel above, which then renders the block from the carried state: the result never depends on convergence.
-constexpr int kEnvMwRounds = 8;
-constexpr int kEnvMwNW = 8, kEnvMwT = 16, kEnvMwWindow = kEnvMwNW * 64 * kEnvMwT;      // 8192
-struct EnvMwCtl {
-    int moved[kEnvMwRounds + 1];
-    int fallback;
-};
-template <bool PEAK>
-__global__ void __launch_bounds__(kEnvMwNW * 64)
-k_env_newton_mw(float *out, const float *in, const double *det, int64_t n, int channels, double attack_coeff,
-                double release_coeff, const double *state, int round, int nwin, double *pa_buf, double *pb_buf,
-                double *guess, EnvMwCtl *ctl) {
-    constexpr int NW = kEnvMwNW, T = kEnvMwT, kWindow = kEnvMwWindow, kThreads = NW * 64;
-    __shared__ double s_a[2][NW], s_b[2][NW], s_pa[T + 1], s_pr[T + 1], s_entry;
-    __shared__ int s_moved[2][NW];
-    using Raw = typename std::conditional<PEAK, float, double>::type;
-    __shared__ Raw s_x[kWindow + kWindow / T];
-    __shared__ float s_y[kWindow + kWindow / T];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int w = blockIdx.x, ch = blockIdx.y;
-    if (round > 0 && ctl->moved[round - 1] == 0) return;         // converged in an earlier round
-    const int64_t base = (int64_t)w * kWindow;
-    const int cur = round & 1, prev = cur ^ 1;
-    double *pa_cur = pa_buf + ((int64_t)cur * channels + ch) * nwin, *pb_cur = pb_buf + ((int64_t)cur * channels + ch) * nwin;
-    const double *pa_prev = pa_buf + ((int64_t)prev * channels + ch) * nwin;
-    const double *pb_prev = pb_buf + ((int64_t)prev * channels + ch) * nwin;
-
-    // request the window's frames first: their latency covers the fold below
-    Raw raw[T];
-#pragma unroll
-    for (int i = 0; i < T; ++i) {
-        int64_t f = base + i * kThreads + tid;
-        f = f < n ? f : n - 1;
-        if constexpr (PEAK) raw[i] = in[f * channels + ch];
-        else raw[i] = det[f * channels + ch];
-    }
-    if (tid == 0) {
-        double pa = 1.0, pr = 1.0;
-        for (int k = 0; k <= T; ++k) {
-            s_pa[k] = pa;
-            s_pr[k] = pr;
-            pa = pa * (1.0 - attack_coeff);
-            pr = pr * (1.0 - release_coeff);
-        }
-    }
-    // entry level: the carried level pushed through the pieces of windows 0..w-1 (wave 0: lanes compose runs of
-    // pieces, then a scan over the lanes)
-    if (wave == 0) {
-        double a = 1.0, b = 0.0;
-        if (round > 0) {
-            const int per = (w + 63) / 64;
-            const int v0 = lane * per, v1 = (v0 + per < w) ? v0 + per : w;
-            for (int v = v0; v < v1; ++v) {
-                const double av = pa_prev[v], bv = pb_prev[v];
-                b = __builtin_fma(av, b, bv);
-                a = a * av;
-            }
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
-                const double ao = __shfl_up(a, d, 64), bo = __shfl_up(b, d, 64);
-                if (lane >= d) {
-                    b = __builtin_fma(a, bo, b);
-                    a = a * ao;
-                }
-            }
-        }
-        if (lane == 63) s_entry = __builtin_fma(a, state[ch], b);
-    }
-    __syncthreads();
-    const double e_in = s_entry;
-    if (round > 0) {
-        const double g = guess[(int64_t)ch * nwin + w];
-        if (fabs(e_in - g) <= kEnvSettled * (fabs(e_in) + fabs(g))) {      // rendered from this entry already
-            if (tid == 0) {
-                pa_cur[w] = pa_prev[w];
-                pb_cur[w] = pb_prev[w];
-            }
-            return;
-        }
-    }
-    if (tid == 0) {
-        ctl->moved[round] = 1;
-        guess[(int64_t)ch * nwin + w] = e_in;
-    }
-#pragma unroll
-    for (int i = 0; i < T; ++i) {
-        const int k = i * kThreads + tid;
-        s_x[k + k / T] = raw[i];
-    }
-    __syncthreads();
-    double t[T];
-#pragma unroll
-    for (int j = 0; j < T; ++j) {
-        const Raw v = s_x[tid * (T + 1) + j];
-        t[j] = PEAK ? fabs((double)v) : (double)v;
-    }
-    const int64_t f0 = base + (int64_t)tid * T;
-    const int live = (n - f0 >= T) ? T : (n - f0 > 0 ? (int)(n - f0) : 0);
-    double entry = e_in, a_tot = 1.0, b_tot = 0.0;
-    double y[T];
-    for (int rnd = 0; rnd <= NW * 64 + 1; ++rnd) {
-        double e = entry;
-        int attacks = 0;
-#pragma unroll
-        for (int j = 0; j < T; ++j) {
-            const bool on = j < live;
-            const bool attack = t[j] > e;
-            const double stepped = e + (attack ? attack_coeff : release_coeff) * (t[j] - e);
-            attacks += (on && attack) ? 1 : 0;
-            e = on ? stepped : e;
-            y[j] = e;
-        }
-        double a = s_pa[attacks] * s_pr[live - attacks];
-        double b = __builtin_fma(-a, entry, e);
-#define PGX_ENV_STEP(CTRL, MASK)                                            \
-        {                                                                   \
-            const double ao = dpp_f64_keep<CTRL, MASK>(1.0, a);             \
-            const double bo = dpp_f64_keep<CTRL, MASK>(0.0, b);             \
-            b = __builtin_fma(a, bo, b);                                    \
-            a = a * ao;                                                     \
-        }
-        PGX_ENV_STEP(0x111, 0xf) PGX_ENV_STEP(0x112, 0xf) PGX_ENV_STEP(0x114, 0xf) PGX_ENV_STEP(0x118, 0xf)
-        PGX_ENV_STEP(0x142, 0xa) PGX_ENV_STEP(0x143, 0xc)
-#undef PGX_ENV_STEP
-        const int buf = rnd & 1;
-        if (lane == 63) {
-            s_a[buf][wave] = a;
-            s_b[buf][wave] = b;
-        }
-        __syncthreads();
-        double cw = e_in, ta = 1.0, tb = 0.0;
-#pragma unroll
-        for (int v = 0; v < NW; ++v) {
-            const double wa = s_a[buf][v], wb = s_b[buf][v];
-            if (v < wave) cw = __builtin_fma(wa, cw, wb);
-            tb = __builtin_fma(wa, tb, wb);                       // the window's piece: exit = ta * entry + tb
-            ta = ta * wa;
-        }
-        a_tot = ta;
-        b_tot = tb;
-        const double aex = dpp_f64_keep<0x138, 0xf>(1.0, a);
-        const double bex = dpp_f64_keep<0x138, 0xf>(0.0, b);
-        const double fresh = __builtin_fma(aex, cw, bex);
-        const bool moved = live > 0 && fabs(fresh - entry) > kEnvSettled * (fabs(fresh) + fabs(entry));
-        entry = fresh;
-        const bool wave_moved = __ballot(moved) != 0ull;
-        if (lane == 0) s_moved[buf][wave] = wave_moved ? 1 : 0;
-        __syncthreads();
-        int any = 0;
-#pragma unroll
-        for (int v = 0; v < NW; ++v) any |= s_moved[buf][v];
-        if (!any) break;
-    }
-#pragma unroll
-    for (int j = 0; j < T; ++j) s_y[tid * (T + 1) + j] = (float)y[j];
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < T; ++i) {
-        const int k = i * kThreads + tid;
-        if (base + k < n) out[(base + k) * channels + ch] = s_y[k + k / T];
-    }
-    if (tid == 0) {
-        pa_cur[w] = a_tot;
-        pb_cur[w] = b_tot;
-    }
-}
-
-// After the last round: converged -> the new carried level is the carried level pushed through every piece;
-// otherwise arm the sequential kernel.
-__global__ void __launch_bounds__(64)
-k_env_mw_finish(double *state, int channels, int nwin, const double *pa_buf, const double *pb_buf, EnvMwCtl *ctl,
-                int rounds) {
-    const int lane = threadIdx.x;
-    int last = 0;                                                 // the last round in which a window moved
-    for (int r = 0; r < rounds; ++r)
-        if (ctl->moved[r]) last = r;
-    const bool converged = last < rounds - 1;                     // a later round ran and found nothing to move
-    if (!converged) {
-        if (lane == 0 && blockIdx.x == 0) ctl->fallback = 1;
-        return;
-    }
-    // pieces of the converged configuration: published by the last round that ran to its end, i.e. `last` (a round
-    // in which nothing moved republishes the same pieces); round last + 1, if launched, returned at once
-    const int ch = blockIdx.x;
-    const int cur = (last + 1) & 1;                               // that later round republished every piece
-    const double *pa = pa_buf + ((int64_t)cur * channels + ch) * nwin, *pb = pb_buf + ((int64_t)cur * channels + ch) * nwin;
-    double a = 1.0, b = 0.0;
-    const int per = (nwin + 63) / 64;
-    const int v0 = lane * per, v1 = (v0 + per < nwin) ? v0 + per : nwin;
-    for (int v = v0; v < v1; ++v) {
-        b = __builtin_fma(pa[v], b, pb[v]);
-        a = a * pa[v];
-    }
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const double ao = __shfl_up(a, d, 64), bo = __shfl_up(b, d, 64);
-        if (lane >= d) {
-            b = __builtin_fma(a, bo, b);
-            a = a * ao;
-        }
-    }
-    if (lane == 63) state[ch] = __builtin_fma(a, state[ch], b);
-}
-
-// ================================================================================================
-// TransformPE: chains of named element-wise float64 operations (pygmu2_amd/transforms.py)
-// ================================================================================================
-__global__ void __launch_bounds__(kBlock)
-k_transform(float *out, const float *in, int64_t n_elems, const pgx_transform_op *ops, int nops) {
-    const int64_t stride = (int64_t)gridDim.x * kBlock;
-    for (int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x; e < n_elems; e += stride) {
-        double v = (double)in[e];
-        for (int k = 0; k < nops; ++k) {
-            const pgx_transform_op op = ops[k];
-            switch (op.code) {
-            case 0: v = op.p1 + op.p0 * v; break;                              // affine: offset + scale*x
-            case 1: v = v < op.p0 ? op.p0 : (v > op.p1 ? op.p1 : v); break;    // clip (NaN passes through)
-            case 2: v = sqrt(v); break;                                        // x ** 0.5 (numpy -> sqrt)
-            case 3: v = v * v; break;                                          // x ** 2 (numpy -> square)
-            case 4: v = fabs(v); break;
-            case 5: v = tanh(v); break;
-            case 6: v = 1.0 - v; break;
-            default: break;
-            }
-        }
-        out[e] = (float)v;
-    }
-}
-
 }  // namespace
 
 // ================================================================================================ C ABI
 extern "C" {
-
-size_t pgx_biquad_workspace_bytes(int batch, int64_t n, int channels, int64_t settle_frames) {
-    if (batch <= 0 || n <= 0 || channels <= 0) return 0;
-    // a caller that passes settle_frames > 0 also passes tables; without them the exact pair may run
-    if (settle_frames > 0 && biquad_settled_plan(batch, n, channels, settle_frames, true).ok) return 0;
-    BqPlan p = biquad_plan(batch, n, channels);
-    if (p.nseg <= 1) return 0;
-    size_t chains = (size_t)batch * channels;
-    return (chains * 2 + chains * (size_t)p.nseg * 2) * sizeof(double);
-}
-
-size_t pgx_biquad_table_doubles(void) { return kBqTableDoubles; }
-
-int pgx_biquad_tables(double *tables, const double *coef, int batch) {
-    PGX_REQUIRE_INIT();
-    if (batch <= 0) return PGX_OK;
-    PGX_CHECK_ARG(tables && coef, "pgx_biquad_tables: bad argument");
-    hipLaunchKernelGGL(k_biquad_tables, dim3(batch), dim3(64), 0, pgx::stream(), tables, coef);
-    PGX_LAUNCH_CHECK("k_biquad_tables");
-    return PGX_OK;
-}
-
-int pgx_biquad_const(float *out, int64_t out_stride, const float *in, int64_t in_stride, int batch, int64_t n,
-                     int channels, const double *coef, const double *tables, int64_t settle_frames, double *state,
-                     void *workspace) {
-    PGX_REQUIRE_INIT();
-    if (n <= 0 || batch <= 0) return PGX_OK;
-    PGX_CHECK_ARG(out && in && coef && state && channels >= 1, "pgx_biquad_const: bad argument");
-    PGX_CHECK_ARG(batch == 1 || (out_stride >= n * channels && in_stride >= n * channels),
-                  "pgx_biquad_const: instance stride too small");
-    PGX_CHECK_ARG((int64_t)batch * channels <= 65535, "pgx_biquad_const: too many chains");
-    int chains = batch * channels;
-    const BqSettledPlan sp = biquad_settled_plan(batch, n, channels, settle_frames, tables != nullptr);
-    if (sp.ok) {
-        const dim3 grid(sp.groups == 1 ? 1 : (sp.groups + 7) / 8 * 8, chains);
-        if (channels == 1)
-            hipLaunchKernelGGL((k_biquad_settled<true, true>), grid, dim3(kSbBlock), 0, pgx::stream(), out,
-                               out_stride, in, in_stride, n, channels, coef, tables, state, sp.seg, sp.head,
-                               sp.tail, sp.warm, sp.groups);
-        else
-            hipLaunchKernelGGL((k_biquad_settled<false, false>), grid, dim3(kSbBlock), 0, pgx::stream(), out,
-                               out_stride, in, in_stride, n, channels, coef, tables, state, sp.seg, sp.head,
-                               sp.tail, sp.warm, sp.groups);
-        PGX_LAUNCH_CHECK("k_biquad_settled");
-        return PGX_OK;
-    }
-    BqPlan p = biquad_plan(batch, n, channels);
-    dim3 grid(p.nseg, chains);
-    if (p.nseg > 1) {
-        PGX_CHECK_ARG(workspace != nullptr, "pgx_biquad_const: workspace required for this size");
-        double *snap = (double *)workspace;
-        double *agg = snap + (size_t)chains * 2;
-        hipLaunchKernelGGL(k_biquad_const<0>, grid, dim3(kBlock), 0, pgx::stream(), out, out_stride, in,
-                           in_stride, n, channels, coef, state, (const double *)snap, agg, p.seg_tiles, p.nseg);
-        PGX_LAUNCH_CHECK("k_biquad_const<reduce>");
-        hipLaunchKernelGGL(k_biquad_const<1>, grid, dim3(kBlock), 0, pgx::stream(), out, out_stride, in,
-                           in_stride, n, channels, coef, state, (const double *)snap, agg, p.seg_tiles, p.nseg);
-        PGX_LAUNCH_CHECK("k_biquad_const<apply>");
-    } else {
-        hipLaunchKernelGGL(k_biquad_const<1>, grid, dim3(kBlock), 0, pgx::stream(), out, out_stride, in,
-                           in_stride, n, channels, coef, state, (const double *)nullptr, (double *)nullptr,
-                           p.seg_tiles, p.nseg);
-        PGX_LAUNCH_CHECK("k_biquad_const");
-    }
-    return PGX_OK;
-}
-
-// The sine-source variant: 4-wave workgroups, three per CU (PGX_SB_SINE_BLOCK=512: the 8-wave form, one per CU --
-// experiments)
-static int sine_block() {
-    static const int block = getenv("PGX_SB_SINE_BLOCK") ? atoi(getenv("PGX_SB_SINE_BLOCK")) : 256;
-    return block == 512 ? 512 : 256;
-}
-static BqSettledPlan biquad_sine_plan(int64_t n, int64_t settle_frames) {
-    static const int want = getenv("PGX_SB_SINE_WGS") ? atoi(getenv("PGX_SB_SINE_WGS")) : (sine_block() == 256 ? 1024 : 512);
-    return biquad_settled_plan(1, n, 1, settle_frames, true, want);
-}
-
-int pgx_biquad_sine_supported(int64_t n, int64_t settle_frames) {
-    return (n > 0 && biquad_sine_plan(n, settle_frames).ok) ? 1 : 0;
-}
-
-// Wave runs (k_biquad_sine_runs) for window-sized blocks.  The grid is one resident round: the occupancy the runtime
-// reports for the kernel times the CUs, taken once.
-constexpr int64_t kRunMinChunks = 4;     // a wave's run below this: the current kernel (measured faster from 16 M frames on)
-static int runs_resident_waves() {
-    static const int waves = [] {
-        int blocks = 0, cus = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, k_biquad_sine_runs, kRunBlock, 0) != hipSuccess ||
-            hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, pgx::device_index()) != hipSuccess)
-            return 0;
-        return blocks * cus * (kRunBlock / 64);
-    }();
-    return waves;
-}
-// The shortest run (in chunks) the wave runs take: PGX_SB_SINE_RUNS=0 forces the current kernel (A/B runs), another
-// value replaces kRunMinChunks; pgx_biquad_sine_set_runs overrides it
-static int &runs_min_chunks() {
-    static int v = getenv("PGX_SB_SINE_RUNS") ? atoi(getenv("PGX_SB_SINE_RUNS")) : (int)kRunMinChunks;
-    return v;
-}
-
-struct RunsPlan {
-    bool ok;
-    int run, head, tail, warm, waves;    // in 1024-frame chunks; waves used
-};
-static RunsPlan biquad_sine_runs_plan(int64_t n, int64_t settle_frames) {
-    RunsPlan p{};
-    const int resident = runs_resident_waves();
-    const int min_chunks = runs_min_chunks();
-    if (min_chunks <= 0 || resident <= 0 || settle_frames <= 0) return p;
-    const int64_t chunks = pgx::ceil_div(n, (int64_t)kRunChunk);
-    const int64_t warm = pgx::ceil_div(settle_frames, (int64_t)kRunChunk);
-    const int64_t run = pgx::ceil_div(chunks, (int64_t)resident);
-    if (run < min_chunks || run < 4 * warm) return p;       // short runs, or a warm-up above 1/4 of the work
-    const int64_t head = run / 2 > warm ? run / 2 : warm;    // wave 0: head + tail = one run
-    const int64_t tail = run - head > 1 ? run - head : 1;
-    if (chunks <= head + tail) return p;
-    p.ok = true;
-    p.run = (int)run;
-    p.head = (int)head;
-    p.tail = (int)tail;
-    p.warm = (int)warm;
-    p.waves = 1 + (int)pgx::ceil_div(chunks - head - tail, run);
-    return p;
-}
-
-int pgx_biquad_sine_set_runs(int min_chunks) {
-    const int was = runs_min_chunks();
-    runs_min_chunks() = min_chunks < 0 ? (int)kRunMinChunks : min_chunks;
-    return was;
-}
-
-int pgx_biquad_sine_runs_plan(int64_t n, int64_t settle_frames, int out[5]) {
-    if (!out || n <= 0 || !pgx::initialised()) return 0;
-    const RunsPlan rp = biquad_sine_runs_plan(n, settle_frames);
-    if (!rp.ok || !biquad_sine_plan(n, settle_frames).ok) return 0;
-    out[0] = rp.run;
-    out[1] = rp.head;
-    out[2] = rp.tail;
-    out[3] = rp.warm;
-    out[4] = rp.waves;
-    return 1;
-}
-
-// Deadline pacing of the wave runs (RunsPace).  PGX_SB_SINE_PACING=0 / 1 replaces the default,
-// pgx_biquad_sine_set_pacing overrides it; PGX_SB_SINE_PACE_FACTOR replaces kPaceFactor (experiments).
-constexpr int kPaceDefault = 1;
-constexpr float kPaceFactor = 1.0f;      // tau = the previous window's longest wave / (run + warm) x this
-static int &runs_pacing() {
-    static int v = getenv("PGX_SB_SINE_PACING") ? (atoi(getenv("PGX_SB_SINE_PACING")) != 0) : kPaceDefault;
-    return v;
-}
-static float pace_factor() {
-    static const float f = getenv("PGX_SB_SINE_PACE_FACTOR") ? (float)atof(getenv("PGX_SB_SINE_PACE_FACTOR")) : kPaceFactor;
-    return f;
-}
-// the two device words of RunsPace (made on first use, released by pgx_shutdown), the id of the last runs-launch and
-// its plan: the next launch is paced by its duration only if it has the same plan and follows it directly
-static struct {
-    unsigned long long *words = nullptr;
-    unsigned next_id = 1, last_id = 0;
-    int run = 0, warm = 0, waves = 0;
-} g_pace;
-
-int pgx_biquad_sine_set_pacing(int mode) {
-    const int was = runs_pacing();
-    runs_pacing() = mode < 0 ? kPaceDefault : (mode != 0);
-    return was;
-}
-
-int pgx_biquad_sine_pacing_info(int64_t out[3]) {
-    PGX_REQUIRE_INIT();
-    PGX_CHECK_ARG(out, "pgx_biquad_sine_pacing_info: null output");
-    out[0] = out[1] = out[2] = 0;
-    if (!g_pace.words) return PGX_OK;
-    unsigned long long w[2];
-    PGX_HIP(hipMemcpyAsync(w, g_pace.words, sizeof(w), hipMemcpyDeviceToHost, pgx::stream()));
-    PGX_HIP(hipStreamSynchronize(pgx::stream()));
-    out[0] = (int64_t)(w[0] >> 32);
-    out[1] = (int64_t)(w[0] & 0xffffffffull);
-    out[2] = (w[1] >> 32) == (w[0] >> 32) ? (int64_t)(w[1] & 0xffffffffull) : 0;
-    return PGX_OK;
-}
-
-#ifdef PGX_SB_RUNS_STAMPS
-static int g_runs_stamp_launch = 0;
-// the stamps of the last two window launches, [2][4096][4] ticks of 10 ns; slot = launch number & 1.  Returns the
-// number of launches so far (after a device synchronise).
-extern "C" int pgx_biquad_sine_runs_stamps(unsigned long long *host_out) {
-    if (hipDeviceSynchronize() != hipSuccess ||
-        hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_runs_stamps), sizeof(unsigned long long) * 2 * kRunStampWaves * 4) != hipSuccess)
-        return -1;
-    return g_runs_stamp_launch;
-}
-#endif
-
-int pgx_biquad_sine(float *out, int64_t start, int64_t n, double sample_rate, double w, double amp, double phase0,
-                    const double *coef, const double *tables, int64_t settle_frames, double *state,
-                    double *state_backup) {
-    PGX_REQUIRE_INIT();
-    if (n <= 0) return PGX_OK;
-    PGX_CHECK_ARG(out && coef && tables && state && sample_rate > 0, "pgx_biquad_sine: bad argument");
-    const int block = sine_block();
-    const BqSettledPlan sp = biquad_sine_plan(n, settle_frames);
-    PGX_CHECK_ARG(sp.ok, "pgx_biquad_sine: block too short for the single-launch plan (pgx_biquad_sine_supported)");
-    // the largest phase of the render has to stay in the bounded sine's range
-    const double far = fabs(phase0) + fabs(w) * ((double)(llabs(start) + n) / sample_rate);
-    PGX_CHECK_ARG(far < pgx::kSinFastRange, "pgx_biquad_sine: phase beyond the fast sine range");
-    // the tone's constants (five long-double sines and cosines) are made once per (w, sample rate): a stream of windows
-    // asks for the same tone every time, and they were 1 us of every window opening's host time
-    static SbSine cached;
-    static bool have = false;
-    if (!have || cached.w != w || cached.sr != sample_rate) {
-        SbSine c;
-        c.w = w;
-        c.sr = sample_rate;
-        c.inv_sr = 1.0 / sample_rate;
-        const long double d = (long double)w / (long double)sample_rate;
-        c.cos_d = (double)cosl(d);
-        c.sin_d = (double)sinl(d);
-        c.two_cos_d = (fabsl(sinl(d)) >= 1e-3L) ? (double)(2.0L * cosl(d)) : 0.0;
-        // a tile's advance, block * 16 frames: the angle reduced in long double before the sine and cosine are taken
-        const long double turn = 6.283185307179586476925286766559L;
-        long double a = d * (long double)(sine_block() * kBqT);
-        a -= turn * floorl(a / turn);
-        c.tile_cos = (double)cosl(a);
-        c.tile_sin = (double)sinl(a);
-        cached = c;
-        have = true;
-    }
-    const RunsPlan rp = biquad_sine_runs_plan(n, settle_frames);
-    if (rp.ok) {
-        static SbRuns runs_cached;
-        static bool runs_have = false;
-        if (!runs_have || runs_cached.w != w || runs_cached.sr != sample_rate) {
-            SbRuns c;
-            c.w = cached.w;
-            c.sr = cached.sr;
-            c.inv_sr = cached.inv_sr;
-            c.cos_d = cached.cos_d;
-            c.sin_d = cached.sin_d;
-            c.two_cos_d = cached.two_cos_d;
-            // a chunk's advance, 1024 frames: the angle reduced in long double before the sine and cosine are taken
-            const long double turn = 6.283185307179586476925286766559L;
-            long double a = (long double)w / (long double)sample_rate * (long double)kRunChunk;
-            a -= turn * floorl(a / turn);
-            c.chunk_cos = (double)cosl(a);
-            c.chunk_sin = (double)sinl(a);
-            runs_cached = c;
-            runs_have = true;
-        }
-        SbRuns sine = runs_cached;
-        sine.amp = amp;
-        sine.phase0 = phase0;
-        sine.start = start;
-        sine.state_backup = state_backup;
-        const int groups = (rp.waves + kRunBlock / 64 - 1) / (kRunBlock / 64);
-        RunsPace pace{nullptr, 0, 0, 0.0f};
-        if (runs_pacing()) {
-            if (!g_pace.words) {                               // first use: two zeroed words, in stream order
-                void *p = nullptr;
-                PGX_HIP(hipMalloc(&p, 2 * sizeof(unsigned long long)));
-                g_pace.words = (unsigned long long *)p;
-                PGX_HIP(hipMemsetAsync(p, 0, 2 * sizeof(unsigned long long), pgx::stream()));
-            }
-            pace.words = g_pace.words;
-            if (g_pace.next_id == 0) {                         // the ids wrap: start over, or no new id would dominate
-                PGX_HIP(hipMemsetAsync(g_pace.words, 0, 2 * sizeof(unsigned long long), pgx::stream()));
-                g_pace.next_id = 1;
-                g_pace.last_id = 0;
-            }
-            pace.id = g_pace.next_id++;
-            if (g_pace.last_id && g_pace.run == rp.run && g_pace.warm == rp.warm && g_pace.waves == rp.waves)
-                pace.prev_id = g_pace.last_id;
-            pace.per_chunk = pace_factor() / (float)(rp.run + rp.warm);
-            g_pace.last_id = pace.id;
-            g_pace.run = rp.run;
-            g_pace.warm = rp.warm;
-            g_pace.waves = rp.waves;
-        } else {
-            g_pace.last_id = 0;
-        }
-#ifdef PGX_SB_RUNS_STAMPS
-        hipLaunchKernelGGL(k_biquad_sine_runs, dim3(groups), dim3(kRunBlock), 0, pgx::stream(), out, n, coef, tables,
-                           state, rp.run, rp.head, rp.tail, rp.warm, rp.waves, sine, pace, g_runs_stamp_launch++);
-#else
-        hipLaunchKernelGGL(k_biquad_sine_runs, dim3(groups), dim3(kRunBlock), 0, pgx::stream(), out, n, coef, tables,
-                           state, rp.run, rp.head, rp.tail, rp.warm, rp.waves, sine, pace);
-#endif
-        PGX_LAUNCH_CHECK("k_biquad_sine_runs");
-        return PGX_OK;
-    }
-    g_pace.last_id = 0;                                        // a render between two windows: the next one runs unpaced
-    SbSine sine = cached;
-    sine.amp = amp;
-    sine.phase0 = phase0;
-    sine.start = start;
-    sine.state_backup = state_backup;
-    const dim3 grid(sp.groups == 1 ? 1 : (sp.groups + 7) / 8 * 8, 1);
-    if (block == 256)
-        hipLaunchKernelGGL((k_biquad_settled<true, true, true, 256>), grid, dim3(256), 0, pgx::stream(), out,
-                           (int64_t)0, (const float *)nullptr, (int64_t)0, n, 1, coef, tables, state, sp.seg, sp.head,
-                           sp.tail, sp.warm, sp.groups, sine);
-    else
-        hipLaunchKernelGGL((k_biquad_settled<true, true, true>), grid, dim3(kSbBlock), 0, pgx::stream(), out,
-                           (int64_t)0, (const float *)nullptr, (int64_t)0, n, 1, coef, tables, state, sp.seg, sp.head,
-                           sp.tail, sp.warm, sp.groups, sine);
-    PGX_LAUNCH_CHECK("k_biquad_settled<sine>");
-    return PGX_OK;
-}
 
 // A = 10^(gain_db/40) is a host-side Python float pow in the reference (biquad_pe.py:250); the
 // binding passes it and its square root by value so the device never calls pow().
@@ -5422,68 +3087,6 @@ int pgx_supersaw_wide(float *out, int64_t out_stride, int batch, int nvoices, in
     return PGX_OK;
 }
 
-int pgx_gate_stateful(float *out, int64_t n, double sample_rate, double freq, double duty, double phase,
-                      const float *freq_stream, const float *duty_stream, const float *phase_stream, double *state) {
-    PGX_REQUIRE_INIT();
-    if (n <= 0) return PGX_OK;
-    PGX_CHECK_ARG(out && state && sample_rate > 0, "pgx_gate_stateful: bad argument");
-    hipLaunchKernelGGL(k_gate_stateful, dim3(1), dim3(kBlock), 0, pgx::stream(), out, n, sample_rate, freq, duty,
-                       phase, freq_stream, duty_stream, phase_stream, state);
-    PGX_LAUNCH_CHECK("k_gate_stateful");
-    return PGX_OK;
-}
-
-int pgx_sine_stateful(float *out, int64_t n, int channels, double sample_rate,
-                      const pgx_sine_stateful_params *params, const float *freq, const float *amp,
-                      const float *phase_mod, double *state) {
-    PGX_REQUIRE_INIT();
-    if (n <= 0) return PGX_OK;
-    PGX_CHECK_ARG(out && params && state && channels >= 1 && sample_rate > 0, "pgx_sine_stateful: bad argument");
-    hipLaunchKernelGGL(k_sine_stateful, dim3(1), dim3(kBlock), 0, pgx::stream(), out, n, channels, sample_rate,
-                       params, freq, amp, phase_mod, state);
-    PGX_LAUNCH_CHECK("k_sine_stateful");
-    return PGX_OK;
-}
-
-// A bank of stateful sines.  Without a workspace, or for blocks of up to two tiles: the walk, a workgroup per voice.  With
-// one: a workgroup per tile and voice (k_sine_bank_totals, k_sine_bank_apply).  Row v is pgx_sine_stateful's either way.
-constexpr int64_t kSinBankMaxTiles = (int64_t)1 << 22;          // (grid.x; longer rows are walked)
-
-size_t pgx_sine_stateful_bank_workspace_bytes(int64_t n, int batch) {
-    if (n <= 0 || batch <= 0) return 0;
-    return (size_t)batch * (size_t)(pgx::ceil_div(n, (int64_t)kSinTile) + 2) * sizeof(double);
-}
-
-int pgx_sine_stateful_bank(float *out, int64_t out_stride, int batch, int64_t n, int channels, double sample_rate,
-                           const pgx_sine_stateful_params *params, const float *freq, int64_t freq_stride,
-                           const float *amp, int64_t amp_stride, const float *phase_mod, int64_t phase_stride,
-                           double *state, void *workspace) {
-    PGX_REQUIRE_INIT();
-    if (n <= 0 || batch <= 0) return PGX_OK;
-    PGX_CHECK_ARG(out && params && state && channels >= 1 && sample_rate > 0 && batch <= 65535,
-                  "pgx_sine_stateful_bank: bad argument");
-    PGX_CHECK_ARG(out_stride >= n * channels && (!freq || freq_stride >= n) && (!amp || amp_stride >= n) &&
-                      (!phase_mod || phase_stride >= n),
-                  "pgx_sine_stateful_bank: a stride below its row");
-    const int64_t tiles = pgx::ceil_div(n, (int64_t)kSinTile);
-    if (workspace == nullptr || tiles <= 2 || tiles > kSinBankMaxTiles) {
-        hipLaunchKernelGGL(k_sine_stateful_bank, dim3(batch), dim3(kBlock), 0, pgx::stream(), out, out_stride, n,
-                           channels, sample_rate, params, freq, freq_stride, amp, amp_stride, phase_mod, phase_stride,
-                           state);
-        PGX_LAUNCH_CHECK("k_sine_stateful_bank");
-        return PGX_OK;
-    }
-    double *ws = (double *)workspace;
-    hipLaunchKernelGGL(k_sine_bank_totals, dim3((unsigned)tiles, batch), dim3(kBlock), 0, pgx::stream(), n, sample_rate,
-                       params, freq, freq_stride, (const double *)state, ws, tiles);
-    PGX_LAUNCH_CHECK("k_sine_bank_totals");
-    hipLaunchKernelGGL(k_sine_bank_apply, dim3((unsigned)tiles, batch), dim3(kBlock), 0, pgx::stream(), out, out_stride,
-                       n, channels, sample_rate, params, freq, freq_stride, amp, amp_stride, phase_mod, phase_stride,
-                       state, (const double *)ws, tiles);
-    PGX_LAUNCH_CHECK("k_sine_bank_apply");
-    return PGX_OK;
-}
-
 
 int pgx_svf(float *out, const float *in, int64_t n, int channels, double sample_rate,
             const pgx_biquad_var_params *params, const float *freq, const float *q, double gain_a,
@@ -5546,109 +3149,4 @@ int pgx_svf_bank(float *out, int64_t out_stride, const float *in, int64_t in_str
     return PGX_OK;
 }
 
-constexpr int64_t kEnvMwMinFrames = 16 * (int64_t)kEnvMwWindow;      // from here on all windows at once
-
-size_t pgx_envelope_scratch_bytes(int64_t n, int channels) {
-    if (n <= 0 || channels <= 0) return 0;
-    const size_t base = (size_t)(n + (n + kEnvBlock - 1) / kEnvBlock) * channels;
-    const size_t nwin = (size_t)((n + kEnvMwWindow - 1) / kEnvMwWindow);
-    return (base + 5 * nwin * channels + 8) * sizeof(double);              // + pieces (2 x 2), entries, control
-}
-
-int pgx_envelope(float *out, const float *in, int64_t n, int channels, double attack_coeff,
-                 double release_coeff, int one_pole, int rms_window, int64_t rms_period, double *state,
-                 double *scratch) {
-    PGX_REQUIRE_INIT();
-    if (n <= 0) return PGX_OK;
-    PGX_CHECK_ARG(out && in && state && scratch && channels >= 1, "pgx_envelope: bad argument");
-    const bool fused_peak = !one_pole && rms_window <= 0;                   // |x| is taken inside the follower
-    if (!fused_peak) {
-        double *blocks = scratch + n * channels;                            // after the detector output
-        if (rms_window > 0) {
-            const int64_t items = (n + kEnvBlock - 1) / kEnvBlock * channels;
-            hipLaunchKernelGGL(k_env_blocks, dim3((unsigned)((items + kWaves - 1) / kWaves)), dim3(kBlock), 0,
-                               pgx::stream(), blocks, in, n, channels);
-            PGX_LAUNCH_CHECK("k_env_blocks");
-        }
-        hipLaunchKernelGGL(k_env_detect, dim3(pgx::grid_for(n * channels, kBlock)), dim3(kBlock), 0, pgx::stream(),
-                           scratch, in, blocks, n, channels, rms_window, rms_period);
-        PGX_LAUNCH_CHECK("k_env_detect");
-    }
-    if (one_pole) {
-        hipLaunchKernelGGL(k_env_onepole, dim3(channels), dim3(kBlock), 0, pgx::stream(), out,
-                           (const double *)scratch, n, channels, attack_coeff, state);
-        PGX_LAUNCH_CHECK("k_env_onepole");
-    } else {
-        const double *det = fused_peak ? nullptr : (const double *)scratch;
-        const int *run_flag = nullptr;
-        const int64_t nwin64 = (n + kEnvMwWindow - 1) / kEnvMwWindow;
-        if (n >= kEnvMwMinFrames && nwin64 <= 65535 && channels <= 65535) {
-            // all windows at once, one launch per Newton round over the windows' entry levels
-            const int nwin = (int)nwin64;
-            double *mw = scratch + (size_t)(n + (n + kEnvBlock - 1) / kEnvBlock) * channels;
-            double *pa_buf = mw, *pb_buf = mw + 2 * (size_t)nwin * channels, *guess = mw + 4 * (size_t)nwin * channels;
-            EnvMwCtl *ctl = reinterpret_cast<EnvMwCtl *>(mw + 5 * (size_t)nwin * channels);
-            if (int rc = pgx_memset(ctl, 0, sizeof(EnvMwCtl))) return rc;
-            // (PGX_ENV_MW_ROUNDS=1 makes every block give up: the test of the fallback)
-            static const int rounds_env = getenv("PGX_ENV_MW_ROUNDS") ? atoi(getenv("PGX_ENV_MW_ROUNDS")) : kEnvMwRounds;
-            const int rounds = rounds_env < 1 ? 1 : (rounds_env > kEnvMwRounds ? kEnvMwRounds : rounds_env);
-            for (int r = 0; r < rounds; ++r) {
-                if (fused_peak)
-                    hipLaunchKernelGGL(k_env_newton_mw<true>, dim3(nwin, channels), dim3(kEnvMwNW * 64), 0,
-                                       pgx::stream(), out, in, det, n, channels, attack_coeff, release_coeff,
-                                       (const double *)state, r, nwin, pa_buf, pb_buf, guess, ctl);
-                else
-                    hipLaunchKernelGGL(k_env_newton_mw<false>, dim3(nwin, channels), dim3(kEnvMwNW * 64), 0,
-                                       pgx::stream(), out, in, det, n, channels, attack_coeff, release_coeff,
-                                       (const double *)state, r, nwin, pa_buf, pb_buf, guess, ctl);
-                PGX_LAUNCH_CHECK("k_env_newton_mw");
-            }
-            hipLaunchKernelGGL(k_env_mw_finish, dim3(channels), dim3(64), 0, pgx::stream(), state, channels, nwin,
-                               (const double *)pa_buf, (const double *)pb_buf, ctl, rounds);
-            PGX_LAUNCH_CHECK("k_env_mw_finish");
-            run_flag = &ctl->fallback;                // the sequential kernel below runs only if that gave up
-        }
-#define PGX_ENV_LAUNCH(NW, T, PEAK)                                                                               \
-        hipLaunchKernelGGL((k_env_newton<NW, T, PEAK>), dim3(channels), dim3(NW * 64), 0, pgx::stream(), out, in, det, \
-                           n, channels, attack_coeff, release_coeff, state, run_flag)
-        if (n <= 1024) {
-            if (fused_peak) PGX_ENV_LAUNCH(4, 4, true);
-            else PGX_ENV_LAUNCH(4, 4, false);
-        } else if (n <= 2048) {
-            if (fused_peak) PGX_ENV_LAUNCH(8, 4, true);
-            else PGX_ENV_LAUNCH(8, 4, false);
-        } else if (n <= 4096) {
-            if (fused_peak) PGX_ENV_LAUNCH(8, 8, true);
-            else PGX_ENV_LAUNCH(8, 8, false);
-        } else {                                     // 8192-sample windows: fewest rounds x windows (measured)
-            if (fused_peak) PGX_ENV_LAUNCH(8, 16, true);
-            else PGX_ENV_LAUNCH(8, 16, false);
-        }
-#undef PGX_ENV_LAUNCH
-        PGX_LAUNCH_CHECK("k_env_newton");
-    }
-    return PGX_OK;
-}
-
-int pgx_transform(float *out, const float *in, int64_t n_elems, const pgx_transform_op *ops, int nops) {
-    PGX_REQUIRE_INIT();
-    if (n_elems <= 0) return PGX_OK;
-    PGX_CHECK_ARG(out && in && (ops || nops == 0) && nops >= 0, "pgx_transform: bad argument");
-    hipLaunchKernelGGL(k_transform, dim3(pgx::grid_for(n_elems, kBlock)), dim3(kBlock), 0, pgx::stream(), out,
-                       in, n_elems, ops, nops);
-    PGX_LAUNCH_CHECK("k_transform");
-    return PGX_OK;
-}
-
 }  // extern "C"
-
-namespace pgx {
-
-// pgx_shutdown, with the streams drained: the pacing words go, and with them the history a next pgx_init could not use
-void biquad_sine_pacing_release() {
-    if (g_pace.words) (void)hipFree(g_pace.words);
-    g_pace.words = nullptr;
-    g_pace.last_id = 0;
-}
-
-}  // namespace pgx

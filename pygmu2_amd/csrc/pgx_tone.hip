@@ -1,7 +1,7 @@
 // pgx_tone.hip -- BiquadPE(SinePE) over window-sized blocks in closed form (pgx_biquad_tone).
 //
 // A constant-coefficient section driven by a pure tone answers, once its transient has died (settle_frames), with the
-// same tone scaled by |H(e^jd)| and shifted by arg H(e^jd), d = w / sr.  The window kernels of pgx_scan.hip already assume
+// same tone scaled by |H(e^jd)| and shifted by arg H(e^jd), d = w / sr.  The window kernels of pgx_biquad.hip already assume
 // the settled condition for every wave but the first; they still run the two-pass float64 recurrence, which is what
 // makes a wave own a contiguous run, carry its state and warm up.  Here a frame is
 //     out[i] = float32(amp |H| sin((phase0 + arg H) + w (start + i) / sr))
@@ -43,7 +43,7 @@ constexpr int kToneBlock = 256;
 constexpr int kToneGroups = PGX_TONE_GROUPS;              // groups of four frames per thread
 constexpr int kToneGroupStride = kToneBlock * 4;          // 1024 frames between a thread's groups
 constexpr int kTonePiece = kToneGroupStride * kToneGroups;   // 4096 frames = 16 KB per workgroup
-// the layout of pgx_biquad_tables (pgx_scan.hip k_biquad_tables): A^1024 at 24, A^(16 q) at 28 + 4 q (q < 64), the
+// the layout of pgx_biquad_tables (pgx_biquad.hip k_biquad_tables): A^1024 at 24, A^(16 q) at 28 + 4 q (q < 64), the
 // first rows of A^r (r < 16) at 284; pgx_biquad_tone checks the total against pgx_biquad_table_doubles()
 constexpr int kTabWave = 24, kTabLane = 28, kTabRows = 28 + 4 * 64, kTabDoubles = kTabRows + 2 * 16;
 constexpr double kToneNoiseRatio = 4.0;                   // sum|h| / |H| above this: the chain is declined
@@ -95,7 +95,7 @@ __device__ __forceinline__ void tone_piece(float *__restrict__ out, int64_t n, c
     sn *= a.gain;
     cs *= a.gain;
     // full, aligned groups are stored write-through (sc1) through a buffer resource based at the piece, as the window
-    // kernel of pgx_scan.hip stores its chunks (no dirty lines left for the launch boundary); the resource ends with the
+    // kernel of pgx_biquad.hip stores its chunks (no dirty lines left for the launch boundary); the resource ends with the
     // piece or with the block, so a store beyond either would be dropped
     const int64_t left = n - p0;
     const uint64_t base = (uint64_t)(out + p0);

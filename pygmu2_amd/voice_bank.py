@@ -470,7 +470,7 @@ class _SineModNode(_Node):
 
     _STATE = ("state",)
     _STREAMS = ("frequency", "amplitude", "phase")
-    TILE = 2048                  # frames per tile of the entry (pgx_scan.hip: kSinTile)
+    TILE = 2048                  # frames per tile of the entry (pgx_phase.hip: kSinTile)
 
     @classmethod
     def scratch_bytes(cls, n: int, k: int) -> int:

@@ -1,4 +1,4 @@
-"""pgx_biquad_sine_runs_plan against a Python restatement of the wave-run plan (csrc/pgx_scan.hip
+"""pgx_biquad_sine_runs_plan against a Python restatement of the wave-run plan (csrc/pgx_biquad.hip
 biquad_sine_runs_plan).  The plan is sized by the device's resident waves, so without a device there is no plan to
 hold it against: the test skips."""
 

@@ -1,6 +1,6 @@
 """
 GPU: BiquadPE(SinePE) as ONE launch (pgx_biquad_sine: the sine is generated in registers inside the settled filter
-kernel, csrc/pgx_scan.hip k_biquad_settled<.., SINE>) against the two-PE path and against the oracle
+kernel, csrc/pgx_biquad.hip k_biquad_settled<.., SINE>) against the two-PE path and against the oracle
 (np.sin + scipy.signal.lfilter, biquad_pe.py:383-404 over sine_pe.py:159-175).
 """
 

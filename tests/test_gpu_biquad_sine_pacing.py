@@ -1,5 +1,5 @@
 """
-GPU: deadline pacing of the BiquadPE(SinePE) window kernel (csrc/pgx_scan.hip k_biquad_sine_runs, RunsPace).  A paced
+GPU: deadline pacing of the BiquadPE(SinePE) window kernel (csrc/pgx_biquad.hip k_biquad_sine_runs, RunsPace).  A paced
 wave reads the wall clock once per chunk and sets its issue priority by how far it is behind the schedule the previous
 window's duration gives it.  A priority changes no sample, so every check here is bit for bit: pacing on against off,
 paced windows against unpaced ones, and the read-out (pgx_biquad_sine_pacing_info) says which windows were paced -- the

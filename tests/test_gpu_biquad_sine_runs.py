@@ -1,5 +1,5 @@
 """
-GPU: BiquadPE(SinePE) over window-sized blocks rendered by wave runs (csrc/pgx_scan.hip k_biquad_sine_runs) against
+GPU: BiquadPE(SinePE) over window-sized blocks rendered by wave runs (csrc/pgx_biquad.hip k_biquad_sine_runs) against
 the single-launch filter kernel (k_biquad_settled<.., SINE>, wave runs off) and against the oracle (np.sin +
 scipy.signal.lfilter) on sections: the head, run boundaries, the tail and the last frame.  The carried state and the
 look-ahead snapshot (state_backup) are the current kernel's, and a window continues seamlessly into 1 M-frame blocks.

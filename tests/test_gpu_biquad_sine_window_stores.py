@@ -1,5 +1,5 @@
 """
-GPU: the stores and the launch boundary of the BiquadPE(SinePE) window kernel (csrc/pgx_scan.hip k_biquad_sine_runs).
+GPU: the stores and the launch boundary of the BiquadPE(SinePE) window kernel (csrc/pgx_biquad.hip k_biquad_sine_runs).
 Its full, aligned chunks leave through the kernel's own store helper; a render into a buffer offset by 4 bytes sends the
 same arithmetic through the unaligned path (store_frames), so the two must agree to the bit -- a wrong offset, a dropped
 row or a clobbered register of the store path shows there.  Against the single-launch filter kernel (wave runs off) and

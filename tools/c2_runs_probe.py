@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """pgx_biquad_sine at 16 M, 33 M, 2^26 and 134 M frames: the single-launch filter kernel (wave runs off) against the
 wave-run kernel (k_biquad_sine_runs, forced on at any run length), alternated, HIP-event time per launch (GPU box).
-The wave-run threshold (kRunMinChunks, pgx_scan.hip) is set from these numbers."""
+The wave-run threshold (kRunMinChunks, pgx_biquad.hip) is set from these numbers."""
 import json, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench

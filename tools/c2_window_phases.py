@@ -4,7 +4,7 @@
     time per launch = fixed cost + rounds x cost per round          (a round: one 1024-frame chunk per resident wave)
 
 for the default build with deadline pacing off and on (a switch of the library, not a build), the build without the hot
-path's stores (PGX_SB_RUNS_NO_STORE, csrc/pgx_scan.hip) and the store, prologue and priority variants that were measured
+path's stores (PGX_SB_RUNS_NO_STORE, csrc/pgx_biquad.hip) and the store, prologue and priority variants that were measured
 and not kept (experiments/c2_window_variants.patch), and from the
 PGX_SB_RUNS_STAMPS build each wave's own clock: the prologue, the first chunk, the spread of the waves' exits and the idle
 time between one launch's last exit and the next one's first entry.
@@ -14,7 +14,7 @@ time between one launch's last exit and the next one's first entry.
     python tools/c2_window_phases.py run --only default,plain_serial
     python tools/c2_window_phases.py run --only default_unpaced,default_paced,stamps_unpaced,stamps_paced
 
-`build` compiles csrc/pgx_scan.hip (with --patched: a patched copy of it) once per variant and links it with the other
+`build` compiles csrc/pgx_biquad.hip (with --patched: a patched copy of it) once per variant and links it with the other
 objects of the last library build (pygmu2_amd/csrc/_obj).  `run` writes c2_window_phases.jsonl (raw rows) and
 c2_window_phases.md (medians and fits) into DIR (default: runs/).
 The fit takes fixed cost and cost per round from the two sizes that fit the 256 MB memory-side cache (64 and 132 MB),
@@ -82,15 +82,16 @@ def build(only=None, patched=False):
     sys.path.insert(0, ROOT)
     from pygmu2_amd import build as B
     B.build()
-    source, variants = os.path.join(B.CSRC, "pgx_scan.hip"), dict(VARIANTS)
+    unit = "pgx_biquad.hip"                                  # the unit that holds k_biquad_sine_runs
+    source, variants = os.path.join(B.CSRC, unit), dict(VARIANTS)
     if patched:
         os.makedirs(VDIR, exist_ok=True)
-        source = os.path.join(VDIR, "pgx_scan_variants.hip")
-        subprocess.check_call(["patch", "-s", "-o", source, os.path.join(B.CSRC, "pgx_scan.hip"),
+        source = os.path.join(VDIR, "pgx_biquad_variants.hip")
+        subprocess.check_call(["patch", "-s", "-o", source, os.path.join(B.CSRC, unit),
                                os.path.join(ROOT, "experiments", "c2_window_variants.patch")])
         variants.update(PATCHED)
     obj_dir = os.path.join(B.CSRC, "_obj")
-    others = [os.path.join(obj_dir, s.replace(".hip", ".o")) for s in B.SOURCES if s != "pgx_scan.hip"]
+    others = [os.path.join(obj_dir, s.replace(".hip", ".o")) for s in B.SOURCES if s != unit]
     os.makedirs(VDIR, exist_ok=True)
     flags = [f for f in B.FLAGS if f != "-shared"]
     def one(item):

@@ -55,11 +55,12 @@ def classify(op: str) -> str:
     return "other"
 
 
-def assembly(source: str) -> str:
+def assembly(source: str, flags=FLAGS, csrc=CSRC, include=os.path.join(ROOT, "include")) -> str:
+    """The gfx950 device assembly of one unit of `csrc` (tools/isa_diff.py compiles another tree's with the library's flags)."""
     with tempfile.TemporaryDirectory() as tmp:
         out = os.path.join(tmp, "k.s")
-        cmd = ["/opt/rocm/bin/hipcc"] + FLAGS + ["-I" + os.path.join(ROOT, "include"), "-I" + CSRC,
-                                                 "--cuda-device-only", "-S", "-o", out, os.path.join(CSRC, source)]
+        cmd = ["/opt/rocm/bin/hipcc"] + flags + ["-I" + include, "-I" + csrc,
+                                                 "--cuda-device-only", "-S", "-o", out, os.path.join(csrc, source)]
         subprocess.check_call(cmd, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
         with open(out) as f:
             return f.read()
@@ -148,11 +149,11 @@ def slots(counts) -> float:
 # float64 slots is taken.
 KERNELS = {
     "k_biquad_settled<mono, staged, sine, 256>": dict(
-        source="pgx_scan.hip", match="k_biquad_settledILb1ELb1ELb1ELi256", depth=2, units=16, unit="frame",
+        source="pgx_biquad.hip", match="k_biquad_settledILb1ELb1ELb1ELi256", depth=2, units=16, unit="frame",
         why="the loop over a workgroup's tiles; a lane makes the 16 frames of its slot per tile (sine rotation, "
             "zero-state pass, DPP scan, carry-in pass)"),
     "k_biquad_settled<mono, staged, 512>": dict(
-        source="pgx_scan.hip", match="k_biquad_settledILb1ELb1ELb0ELi512", depth=2, units=16, unit="frame",
+        source="pgx_biquad.hip", match="k_biquad_settledILb1ELb1ELb0ELi512", depth=2, units=16, unit="frame",
         why="the loop over a workgroup's tiles; 16 frames per lane and tile"),
     "k_supersaw_wide<4>": dict(
         source="pgx_scan.hip", match="k_supersaw_wideILi4", depth=2, units=16, unit="oscillator-frame",

@@ -1,5 +1,5 @@
 #!/bin/bash
-# usage: tools/kernel_resources.sh pgx_scan.hip [name-filter]
+# usage: tools/kernel_resources.sh pgx_biquad.hip [name-filter]
 # VGPR / SGPR / LDS / scratch / occupancy of every kernel of one translation unit (clang's
 # -Rpass-analysis=kernel-resource-usage; cross-compiles, no GPU needed).
 root=$(cd "$(dirname "$0")/.." && pwd)
