@@ -489,6 +489,21 @@ int pgx_stream_range(double *partials_dev, int parts, const float *x, int64_t n)
  * transition: 0 step, 1 linear, 2 exponential, 3 sigmoid, 4 constant_power. */
 int pgx_piecewise(float *out, int64_t start, int64_t n, int channels, const int64_t *times,
                   const double *values, int count, int transition, int hold_first, int hold_last);
+/* PortamentoPE._render (portamento_pe.py:154-254 as its docstring states it): `batch` glide lines in one launch on a grid
+ * of (tiles, lines); line b writes n frames of `channels` equal samples at out + b * out_stride (>= n * channels).
+ * Line b's ramps are entries offsets[b] .. offsets[b + 1] - 1 of the four device arrays, ramp_at non-decreasing within
+ * a line.  Ramp i owns the frames [ramp_at[i], ramp_at[i + 1]), the line's last ramp every frame from its ramp_at on, its
+ * first also every frame before; two ramps with one ramp_at: the earlier owns nothing.  At frame s of ramp i, x = s -
+ * ramp_at[i]: x <= 0 gives ramp_from[i], x >= ramp_len[i] gives ramp_to[i], else ramp_from + (ramp_to - ramp_from) *
+ * ((double)x / (double)ramp_len) in float64 (pgx_piecewise's linear transition), rounded once to float32.
+ * A line of one held value is one ramp with ramp_from == ramp_to (any ramp_at, ramp_len >= 1); a line without ramps
+ * (offsets[b + 1] <= offsets[b]) is silent.  A line's table is read from LDS up to 512 ramps, from global memory
+ * beyond.  No workspace.
+ * n <= 0 or batch <= 0: PGX_OK, nothing launched.  A null pointer, channels < 1, out_stride < n * channels,
+ * batch > 65535: PGX_ERR_INVALID, nothing launched. */
+int pgx_portamento(float *out, int64_t out_stride, int batch, int64_t start, int64_t n, int channels,
+                   const int64_t *ramp_at, const int64_t *ramp_len, const double *ramp_from,
+                   const double *ramp_to, const int32_t *offsets /* [batch + 1] into the ramp arrays */);
 /* WavWriterPE / WavReaderPE sample conversion on the device (half the PCIe bytes of float32):
  * libsndfile's PCM_16 rules as python-soundfile configures them (clipping on; the reference's default
  * subtype, wav_writer_pe.py:67): s = x * 32768 saturated to [-32768, 32767], else lrintf; x = s / 32768. */

@@ -8,7 +8,7 @@ AdsrGatedPE, AdsrTriggeredPE, PeriodicGate, PeriodicTrigger, ConstantPE, ArrayPE
 DiracPE, IdentityPE, CachePE, CropPE, SVFilterPE, EnvelopePE, TransformPE, DelayPE, PiecewisePE,
 TriggerRestartPE, ReverbPE, WavWriterPE, WavReaderPE, KarplusStrongPE, AnalogOscPE, WavetablePE, TimeWarpPE,
 SampleHoldPE, TrackHoldPE, SlewLimiterPE, FunctionGenPE, NoisePE, TralfamPE, SlicePE, SetExtentPE, SequencePE,
-ReversePitchEchoPE
+ReversePitchEchoPE, PortamentoPE, ControlPE
 (+ render_to_file, rho_for_decay_db, pitch_to_freq and the other unit conversions).  Snippet payloads live in HBM; all DSP runs in
 hand-written HIP kernels for gfx950 behind the C ABI of include/pygmu_hip.h.
 """
@@ -103,6 +103,12 @@ from .random_select_pe import RandomSelectPE
 # tests/test_oracle_fuzz_golden.py needs an evaluator under oracle/ for every name listed there;
 # tests/test_gpu_reverse_echo.py holds it to fixtures of the reference.
 from .reverse_pitch_echo_pe import ReversePitchEchoPE
+# PortamentoPE and ControlPE: the same arrangement (pg.PortamentoPE and pg.ControlPE work, neither is in __all__): the
+# fuzz census of tests/test_oracle_fuzz_golden.py needs an evaluator under oracle/ for every name listed there;
+# tests/test_portamento_host.py and tests/test_portamento_gpu.py hold the glide line to fixtures of the reference,
+# tests/test_stream_control_pe.py the control.
+from .portamento_pe import PortamentoPE
+from .control_pe import ControlPE
 from .utils import render_to_file
 from . import device, diagnostics
 

@@ -387,6 +387,145 @@ k_piecewise(float *out, int64_t start, int64_t n, int channels, const int64_t *t
 }
 
 // ------------------------------------------------------------------------------------------------
+// PortamentoPE (portamento_pe.py:154-254, what its docstring promises): held pitches with a linear glide at each note's
+// start.  A line is a table of ramps {at, len, from, to} ordered by `at`; ramp i owns [at_i, at_{i+1}), the last one
+// everything from its `at` on, the first also everything before.  Within a ramp the value is k_piecewise's linear
+// transition over [at, at + len], held either side.
+//
+// A workgroup renders runs of kPortaFrames consecutive frames of one line (blockIdx.y), a wave 64 consecutive items of a
+// run: an item is a frame of `channels` samples (VEC == 1), or four frames of a mono line written as one 16-byte store
+// (VEC == 4: the frames before the line's first 16-byte boundary and those after its last whole vector are the `edge`
+// frames of workgroup 0).  Notes last thousands of frames, so a wave almost always lies in one ramp: it searches the
+// `at` column once, for its first frame, and looks at the next ramp's `at`; only when that falls inside the wave does
+// each lane look for its own ramp, outwards from the wave's (porta_upper_near: the ramp is a few entries on at most).
+// A table of up to kPortaLdsRamps ramps is copied to LDS first (16 KiB of a CU's 160: eight workgroups of it fit, which
+// is all the waves a CU holds) and everything is read from there; a longer one is read where it lies.  A launch of this
+// kind is a chain of dependent round trips -- offsets, table, search, the ramp's values -- and LDS takes the last two out
+// of global memory: tools/portamento_probe.py, profiles/portamento_probe.md.
+// ------------------------------------------------------------------------------------------------
+constexpr int kPortaLdsRamps = 512;
+constexpr int kPortaFrames = 1024;
+
+struct PortaTable {
+    const int64_t *at, *len;
+    const double *from, *to;
+    int count;
+};
+
+// first index in [lo, count) whose at > s
+__device__ __forceinline__ int porta_upper(const int64_t *at, int lo, int count, int64_t s) {
+    int hi = count;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (at[mid] <= s) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// the same, probing lo, lo + 1, lo + 3, lo + 7 ... first: one or two reads when the answer is lo or lo + 1
+__device__ __forceinline__ int porta_upper_near(const int64_t *at, int lo, int count, int64_t s) {
+    int hi = lo, step = 1;
+    while (hi < count && at[hi] <= s) {
+        lo = hi + 1;
+        hi += step;
+        step <<= 1;
+    }
+    return porta_upper(at, lo, hi < count ? hi : count, s);
+}
+
+// frame s of the ramp before index u (u >= 1: the first ramp owns the frames before its `at` too)
+__device__ __forceinline__ float porta_value(const PortaTable &T, int u, int64_t s) {
+    if (T.count <= 0) return 0.0f;
+    const int j = u - 1;
+    const double v0 = T.from[j], v1 = T.to[j];
+    const int64_t x = s - T.at[j], len = T.len[j];
+    if (x <= 0) return (float)v0;
+    if (x >= len) return (float)v1;
+    return (float)(v0 + (v1 - v0) * ((double)x / (double)len));
+}
+
+// one workgroup's share of a line whose table is T (in LDS or in global memory: inlined once for each)
+template <int VEC>
+__device__ __forceinline__ void porta_render(float *y, int64_t start, int64_t n, int channels, const PortaTable T) {
+    auto least1 = [](int u) { return u < 1 ? 1 : u; };
+    // VEC == 4: y + head is the line's first 16-byte boundary, `items` whole vectors follow it
+    const int64_t head = VEC == 1 ? 0 : [&] {
+        const int64_t h = (int64_t)((0 - ((uintptr_t)y >> 2)) & 3);
+        return h < n ? h : n;
+    }();
+    const int64_t items = (n - head) / VEC;
+    constexpr int64_t kItems = kPortaFrames / VEC;                  // items per workgroup and run
+    constexpr int kRounds = kItems / kBlock;                        // rounds of kBlock items in a run
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
+    // the workgroup's runs lie side by side, so a wave's frames only move forward: it searches the table once, for its
+    // first frame, and from then on outwards from where it was
+    const int64_t runs = pgx::ceil_div(items, kItems), per_group = pgx::ceil_div(runs, (int64_t)gridDim.x);
+    const int64_t run_first = blockIdx.x * per_group, run_end = run_first + per_group < runs ? run_first + per_group : runs;
+    int ur = porta_upper(T.at, 0, T.count, start + head + (run_first * kItems + wave * 64) * VEC);
+    for (int64_t run = run_first; run < run_end; ++run) {
+#pragma unroll
+        for (int r = 0; r < kRounds; ++r) {
+            const int64_t q0 = run * kItems + r * kBlock + wave * 64;   // wave-uniform
+            if (q0 >= items) break;
+            const int64_t q_end = q0 + 64 < items ? q0 + 64 : items;
+            const int64_t s_lo = start + head + q0 * VEC, s_hi = start + head + q_end * VEC - 1;
+            ur = porta_upper_near(T.at, ur, T.count, s_lo);
+            const int u = least1(ur);
+            const bool one_ramp = u >= T.count || T.at[u] > s_hi;
+            const int64_t q = q0 + lane;
+            if (q >= items) continue;
+            const int64_t f = head + q * VEC;
+            float v[VEC];
+#pragma unroll
+            for (int j = 0; j < VEC; ++j) {
+                const int64_t s = start + f + j;
+                v[j] = porta_value(T, one_ramp ? u : porta_upper_near(T.at, u, T.count, s), s);
+            }
+            if (VEC == 4) {
+                *reinterpret_cast<float4 *>(y + f) = make_float4(v[0], v[1], v[2], v[3]);
+            } else {
+                for (int c = 0; c < channels; ++c) y[f * channels + c] = v[0];
+            }
+        }
+    }
+    if (VEC == 4 && blockIdx.x == 0) {
+        const int64_t tail_first = head + items * VEC;
+        const int64_t edge = head + (n - tail_first);               // at most 3 + 3 frames
+        if ((int64_t)threadIdx.x < edge) {
+            const int64_t f = (int64_t)threadIdx.x < head ? (int64_t)threadIdx.x : tail_first + (threadIdx.x - head);
+            y[f] = porta_value(T, least1(porta_upper(T.at, 0, T.count, start + f)), start + f);
+        }
+    }
+}
+
+template <int VEC>
+__global__ void __launch_bounds__(kBlock)
+k_portamento(float *out, int64_t out_stride, int64_t start, int64_t n, int channels, const int64_t *ramp_at,
+             const int64_t *ramp_len, const double *ramp_from, const double *ramp_to, const int32_t *offsets,
+             int lds_ramps) {
+    __shared__ int64_t lds_at[kPortaLdsRamps], lds_len[kPortaLdsRamps];
+    __shared__ double lds_from[kPortaLdsRamps], lds_to[kPortaLdsRamps];
+    const int b = blockIdx.y;
+    const int first = offsets[b];
+    const PortaTable G{ramp_at + first, ramp_len + first, ramp_from + first, ramp_to + first, offsets[b + 1] - first};
+    float *y = out + (int64_t)b * out_stride;
+    if (G.count <= lds_ramps) {                                     // (the same for every thread of the workgroup)
+        for (int k = threadIdx.x; k < G.count; k += kBlock) {
+            lds_at[k] = G.at[k];
+            lds_len[k] = G.len[k];
+            lds_from[k] = G.from[k];
+            lds_to[k] = G.to[k];
+        }
+        __syncthreads();
+        porta_render<VEC>(y, start, n, channels, PortaTable{lds_at, lds_len, lds_from, lds_to, G.count});
+    } else {
+        porta_render<VEC>(y, start, n, channels, G);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // WAV sample formats: what the reference's writer does to a float32 sample on its way into a PCM_16 file.
 // wav_writer_pe.py:67 opens the file through python-soundfile, whose SoundFile.__init__ switches libsndfile to
 // clipping conversions (SFC_SET_CLIPPING = SF_TRUE); pcm_write_f2les then uses f2s_clip_array (src/pcm.c):
@@ -826,6 +965,34 @@ int pgx_piecewise(float *out, int64_t start, int64_t n, int channels, const int6
     hipLaunchKernelGGL(k_piecewise, dim3(pgx::grid_for(n, kBlock)), dim3(kBlock), 0, pgx::stream(), out, start, n,
                        channels, times, values, count, transition, hold_first, hold_last);
     PGX_LAUNCH_CHECK("k_piecewise");
+    return PGX_OK;
+}
+
+int pgx_portamento(float *out, int64_t out_stride, int batch, int64_t start, int64_t n, int channels,
+                   const int64_t *ramp_at, const int64_t *ramp_len, const double *ramp_from, const double *ramp_to,
+                   const int32_t *offsets) {
+    PGX_REQUIRE_INIT();
+    if (n <= 0 || batch <= 0) return PGX_OK;
+    PGX_CHECK_ARG(out && ramp_at && ramp_len && ramp_from && ramp_to && offsets && channels >= 1,
+                  "pgx_portamento: bad argument");
+    PGX_CHECK_ARG(out_stride >= n * channels, "pgx_portamento: stride too small");
+    PGX_CHECK_ARG(batch <= 65535, "pgx_portamento: batch too large");
+    // PGX_PORTA_LDS_RAMPS (experiments, tools/portamento_probe.py): a lower staging limit; 0 searches global memory
+    const char *lds_env = getenv("PGX_PORTA_LDS_RAMPS");
+    int lds_ramps = lds_env ? atoi(lds_env) : kPortaLdsRamps;
+    if (lds_ramps > kPortaLdsRamps) lds_ramps = kPortaLdsRamps;
+    // a workgroup takes one run of kPortaFrames frames, or as many side by side as it takes for the whole grid to be on
+    // the chip at once (eight workgroups per CU): the table is copied to LDS once per workgroup, not once per run
+    const int64_t runs = pgx::ceil_div(n, kPortaFrames), most = pgx::kNumCU * 8 / batch > 1 ? pgx::kNumCU * 8 / batch : 1;
+    const dim3 grid((unsigned)pgx::ceil_div(runs, pgx::ceil_div(runs, most)), batch), block(kBlock);
+    // one channel: 16-byte stores between each line's first and last 16-byte boundary
+    if (channels == 1)
+        hipLaunchKernelGGL(k_portamento<4>, grid, block, 0, pgx::stream(), out, out_stride, start, n, channels, ramp_at,
+                           ramp_len, ramp_from, ramp_to, offsets, lds_ramps);
+    else
+        hipLaunchKernelGGL(k_portamento<1>, grid, block, 0, pgx::stream(), out, out_stride, start, n, channels, ramp_at,
+                           ramp_len, ramp_from, ramp_to, offsets, lds_ramps);
+    PGX_LAUNCH_CHECK("k_portamento");
     return PGX_OK;
 }
 
