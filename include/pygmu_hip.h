@@ -280,9 +280,10 @@ int pgx_biquad_tone(float *out, int64_t start, int64_t n, double sample_rate, do
                     double b0, double b1, double b2, double a1, double a2, const double *tables,
                     int64_t settle_frames, double *state /* [2] */, double *state_backup /* [2] or NULL */);
 /* The window kernel is bound by its stores, so the size of a stream's windows is its business: the frames per look-ahead
- * window at which the two live float32 mono windows of a stream (the one being served and the one just opened, whose
- * buffers alternate) are still stored at the memory-side cache's rate, not HBM's, and the host's cost of opening a
- * window is spread over as many frames as that allows.  0: no preference.
+ * window at which the one live float32 mono window of a stream (its last block lives in a buffer of its own,
+ * pgx_biquad_tone_window_split below, so the next window rewrites the same buffer) is still stored at the memory-side
+ * cache's rate, not HBM's, and the host's cost of opening a window is spread over as many frames as that allows.
+ * 0: no preference.
  * PGX_TONE_WINDOW_FRAMES replaces the built-in figure (read once).  A host computation: no device is needed. */
 int64_t pgx_biquad_tone_window_frames(void);
 /* A stream opens a window every few microseconds of host time: pgx_biquad_tone_plan evaluates once what
@@ -295,6 +296,19 @@ void *pgx_biquad_tone_plan(double sample_rate, double w, double amp, double phas
 int pgx_biquad_tone_plan_free(void *plan);
 int pgx_biquad_tone_window(const void *plan, float *out, int64_t start, int64_t n, double *state /* [2] */,
                            double *state_backup /* [2] or NULL */);
+/* A stream whose caller keeps the last block it pulled keeps that block's buffer alive.  pgx_biquad_tone_window_split
+ * stores frames [0, n - tail_frames) to out and frames [n - tail_frames, n) to out_tail[0 ...]: with a window's last
+ * block in a small buffer of its own the big one is free the moment the window is used up, and a stream rewrites one
+ * resident buffer instead of two in turn.  Every frame is made by the same thread from the same anchor with the same
+ * arithmetic as in pgx_biquad_tone_window: out | out_tail, state and state_backup hold the same bits.  tail_frames == 0
+ * is pgx_biquad_tone_window; tail_frames == n leaves out untouched.  16-byte stores into the tail need out_tail on a
+ * 16-byte boundary and n - tail_frames a multiple of 4 (else four 4-byte stores).  PGX_ERR_INVALID for tail_frames < 0,
+ * tail_frames > n and tail_frames > 0 without out_tail.
+ * pgx_biquad_tone_split_tail: 1 when streams should render their windows that way, 0 with PGX_TONE_SPLIT_TAIL=0 (read
+ * once), which keeps the two alternating buffers.  A host computation: no device is needed. */
+int pgx_biquad_tone_window_split(const void *plan, float *out, float *out_tail, int64_t tail_frames, int64_t start,
+                                 int64_t n, double *state /* [2] */, double *state_backup /* [2] or NULL */);
+int pgx_biquad_tone_split_tail(void);
 
 /* Time-varying coefficients: _compute_coefficients per sample (biquad_pe.py:217-335) +
  * the direct-form-I recurrence of _biquad_varying_numba (biquad_pe.py:35-62).

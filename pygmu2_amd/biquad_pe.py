@@ -36,9 +36,21 @@ TONE_WINDOWS = os.environ.get("PYGMU_BIQUAD_TONE", "1") != "0"
 
 
 def tone_window_frames() -> int:
-    """Frames per look-ahead window the closed-form window kernel asks for (pgx_biquad_tone_window_frames: two live
-    windows stay in the memory-side cache); 0: no preference."""
+    """Frames per look-ahead window the closed-form window kernel asks for (pgx_biquad_tone_window_frames: the one live
+    window stays in the memory-side cache); 0: no preference."""
     return int(_dev.load_library().pgx_biquad_tone_window_frames())
+
+
+_SPLIT_TAIL = None
+
+
+def tone_split_tail() -> bool:
+    """Streams render the last block of a closed-form window into a buffer of its own (pgx_biquad_tone_split_tail:
+    PGX_TONE_SPLIT_TAIL=0 says no; the library reads it once, so does this)."""
+    global _SPLIT_TAIL
+    if _SPLIT_TAIL is None:
+        _SPLIT_TAIL = bool(_dev.load_library().pgx_biquad_tone_split_tail())
+    return _SPLIT_TAIL
 
 
 class _TonePlan:
@@ -307,16 +319,50 @@ class BiquadPE(ProcessingElement):
         out = new_output(duration, 1)
         backup, self._backup_target = self._backup_target, None      # a look-ahead window's snapshot: the kernel fills it
         if self._takes_tone_window(L, start, duration, w, phase, sr):
-            plan = self._tone_plan
-            if plan is None:                          # the chain's constants, evaluated once: six arguments per window
-                plan = self._tone_plan = _TonePlan(L.pgx_biquad_tone_plan(sr, w, amp, phase, *self._coef_host,
-                                                                          self._tables.ptr, self._settle))
+            plan = self._tone_window_plan(L, sr, w, amp, phase)
             check(L.pgx_biquad_tone_window(plan.handle, out.ptr, start, duration, self._state.ptr, ptr(backup)),
                   "pgx_biquad_tone_window")
             return Snippet(start, out)
         check(L.pgx_biquad_sine(out.ptr, start, duration, sr, w, amp, phase, self._coef.ptr, self._tables.ptr,
                                 self._settle, self._state.ptr, ptr(backup)), "pgx_biquad_sine")
         return Snippet(start, out)
+
+    def _tone_window_plan(self, L, sr: float, w: float, amp: float, phase: float) -> _TonePlan:
+        plan = self._tone_plan
+        if plan is None:                              # the chain's constants, evaluated once: six arguments per window
+            plan = self._tone_plan = _TonePlan(L.pgx_biquad_tone_plan(sr, w, amp, phase, *self._coef_host,
+                                                                      self._tables.ptr, self._settle))
+        return plan
+
+    def _render_window(self, start: int, duration: int, blocks: int):
+        """look_ahead.render: a window of `blocks` caller blocks that the closed-form kernel takes is rendered with its
+        last block in a buffer of its own (pgx_biquad_tone_window_split) -> (Snippet of the blocks before it, that
+        buffer).  A caller that keeps the last snippet it pulled then keeps 4 MB alive and not the window: the window's
+        buffer returns to the pool when the window is used up, the next window gets the same address and the stream
+        rewrites one buffer that stays in the memory-side cache.  None: the window is rendered as usual."""
+        if blocks < 2 or not FUSE_SINE_SOURCE or _diag.is_enabled():
+            return None
+        chain = self._sine_chain()
+        if chain is None or not tone_split_tail():
+            return None
+        w, amp, phase = chain
+        L = lib()
+        sr = float(self.sample_rate)
+        n = duration * blocks
+        ok = self._sine_supported.get(n)
+        if ok is None:
+            ok = self._sine_supported[n] = bool(L.pgx_biquad_sine_supported(n, self._settle))
+        if not ok or abs(phase) + abs(w) * ((abs(start) + n) / sr) >= SINE_FAST_RANGE:
+            return None
+        if not self._takes_tone_window(L, start, n, w, phase, sr):
+            return None
+        self._ensure_state(1)
+        out, tail = new_output(n - duration, 1), new_output(duration, 1)
+        backup, self._backup_target = self._backup_target, None      # the window's snapshot: the kernel fills it
+        plan = self._tone_window_plan(L, sr, w, amp, phase)
+        check(L.pgx_biquad_tone_window_split(plan.handle, out.ptr, tail.ptr, duration, start, n, self._state.ptr,
+                                             ptr(backup)), "pgx_biquad_tone_window_split")
+        return Snippet(start, out), tail
 
     def _takes_tone_window(self, L, start: int, duration: int, w: float, phase: float, sr: float) -> bool:
         """Window-sized renders (the sizes pgx_biquad_sine would hand to its wave-run kernel, 16 M frames and up) of a chain

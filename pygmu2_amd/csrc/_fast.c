@@ -16,7 +16,7 @@
 static PyObject *g_snippet_type, *g_window_type, *g_slow_render, *g_slow_del, *g_diag_dict;
 static PyObject *s_la_win, *s_ra_win, *s_la_last, *s_ra_last, *s_active, *s_shape;
 static Py_ssize_t sn_start, sn_host, sn_dev, sn_shape, sn_ready, sn_copy, sn_base, sn_bank;
-static Py_ssize_t w_first, w_end, w_buf, w_served, w_block;
+static Py_ssize_t w_first, w_end, w_split, w_tail, w_buf, w_served, w_block;
 
 #define SLOT(obj, off) (*(PyObject **)((char *)(obj) + (off)))
 
@@ -105,14 +105,18 @@ static PyObject *fast_render(PyObject *self, PyObject *const *args, Py_ssize_t n
             if (dict) {
                 PyObject *win = PyDict_GetItem(dict, s_la_win);
                 if (win) {
-                    /* the next block of a stream served from a look-ahead window (look_ahead.py) */
+                    /* the next block of a stream served from a look-ahead window (look_ahead.py): rows of its buffer or,
+                     * from the split on, rows of its tail buffer; a pull that lies across the split is not served here */
                     if ((PyObject *)Py_TYPE(win) == g_window_type) {
-                        long long served, end, first, blk;
-                        PyObject *buf = SLOT(win, w_buf);
+                        long long served, end, first, blk, split = 0;
+                        PyObject *buf = SLOT(win, w_buf), *tail = SLOT(win, w_tail);
+                        const int has_tail = tail && tail != Py_None;
                         if (buf && SLOT(win, w_served) && SLOT(win, w_end) && SLOT(win, w_first) && SLOT(win, w_block) &&
                             as_ll(SLOT(win, w_served), &served) && as_ll(SLOT(win, w_end), &end) &&
                             as_ll(SLOT(win, w_first), &first) && as_ll(SLOT(win, w_block), &blk) && s == served &&
-                            s + d <= end && (blk == 0 || d == blk)) {
+                            s + d <= end && (blk == 0 || d == blk) &&
+                            (!has_tail || (SLOT(win, w_split) && as_ll(SLOT(win, w_split), &split) &&
+                                           (s + d <= split || s >= split)))) {
                             PyObject *now = PyLong_FromLongLong(s + d);
                             if (!now) return NULL;
                             PyObject *old = SLOT(win, w_served);
@@ -122,6 +126,7 @@ static PyObject *fast_render(PyObject *self, PyObject *const *args, Py_ssize_t n
                             const int rc = PyDict_SetItem(dict, s_la_last, now);
                             Py_DECREF(now);
                             if (rc < 0) return NULL;
+                            if (has_tail && s >= split) return make_row(args[0], tail, s - split, args[1]);
                             return make_row(args[0], buf, s - first, args[1]);
                         }
                     }
@@ -187,7 +192,8 @@ static PyObject *py_install(PyObject *module, PyObject *args) {
     OFF(sn_start, snippet_type, "_start"); OFF(sn_host, snippet_type, "_host"); OFF(sn_dev, snippet_type, "_dev");
     OFF(sn_shape, snippet_type, "_shape"); OFF(sn_ready, snippet_type, "_ready"); OFF(sn_copy, snippet_type, "_copy");
     OFF(sn_base, snippet_type, "_base"); OFF(sn_bank, snippet_type, "_bank_window");
-    OFF(w_first, window_type, "first"); OFF(w_end, window_type, "end"); OFF(w_buf, window_type, "buf");
+    OFF(w_first, window_type, "first"); OFF(w_end, window_type, "end"); OFF(w_split, window_type, "split");
+    OFF(w_tail, window_type, "tail"); OFF(w_buf, window_type, "buf");
     OFF(w_served, window_type, "served"); OFF(w_block, window_type, "block");
 #undef OFF
     Py_INCREF(snippet_type); Py_INCREF(window_type); Py_INCREF(slow_render); Py_INCREF(slow_del); Py_INCREF(diag_dict);

@@ -79,14 +79,32 @@ __device__ __forceinline__ void tone_steady_state(const ToneArgs &a, int64_t m, 
     zx = (a.b2 * x0 - a.a2 * y0) + (a.b1 * x1 - a.a1 * y1);
 }
 
-// HEAD: workgroup 0's piece, which adds the zero-input response of dz to the frames below settle
-template <bool HEAD>
+// HEAD: workgroup 0's piece, which adds the zero-input response of dz to the frames below settle.
+// SPLIT: frames [split, n) go to tail[0 ...] instead of out[split ...] (0 < split < n or split == 0: the window's last
+// block in a buffer of its own).  Which frame a thread makes, from which anchor and how, does not depend on it: only the
+// address of the store does.  A piece that lies wholly on one side -- all but one -- chooses its destination once,
+// uniformly, and stores as the unsplit kernel does; the one piece that holds the split decides per group of four.
+template <bool HEAD, bool SPLIT>
 __device__ __forceinline__ void tone_piece(float *__restrict__ out, int64_t n, const double *__restrict__ tables,
-                                           const ToneArgs &a, int64_t piece, bool aligned, double dzx, double dzy) {
+                                           const ToneArgs &a, int64_t piece, bool aligned, double dzx, double dzy,
+                                           float *__restrict__ tail, int64_t split, bool tail_aligned) {
     const int tid = threadIdx.x;
     const int64_t p0 = piece * kTonePiece;
     const int64_t f0 = p0 + 4 * tid;
     if (f0 >= n) return;
+    // dst[0] is frame p0 of the piece's destination, which ends in front of frame lim
+    float *dst = out + p0;
+    int64_t lim = n;
+    bool straddle = false;
+    if (SPLIT) {
+        if (p0 >= split) {
+            dst = tail + (p0 - split);
+            aligned = tail_aligned;
+        } else {
+            lim = split;
+            straddle = split < p0 + kTonePiece;
+        }
+    }
     double sn, cs;
     {
         const double t = pgx::pgx_div_by((double)(a.start + f0), a.sr, a.inv_sr);
@@ -97,11 +115,21 @@ __device__ __forceinline__ void tone_piece(float *__restrict__ out, int64_t n, c
     // full, aligned groups are stored write-through (sc1) through a buffer resource based at the piece, as the window
     // kernel of pgx_biquad.hip stores its chunks (no dirty lines left for the launch boundary); the resource ends with the
     // piece or with the block, so a store beyond either would be dropped
-    const int64_t left = n - p0;
-    const uint64_t base = (uint64_t)(out + p0);
+    const int64_t left = lim - p0;
+    const uint64_t base = (uint64_t)dst;
     const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)base), hi = __builtin_amdgcn_readfirstlane((uint32_t)(base >> 32));
     __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
         (void *)(((uint64_t)hi << 32) | lo), 0, (int)(left < kTonePiece ? left : kTonePiece) * 4, 0x00020000);
+    // the piece that holds the split: a second resource, based at the tail, which ends with the piece or with the block
+    __amdgpu_buffer_rsrc_t rsrc_tail = rsrc;
+    if (SPLIT && straddle) {
+        const uint64_t tbase = (uint64_t)tail;
+        const uint32_t tlo = __builtin_amdgcn_readfirstlane((uint32_t)tbase),
+                       thi = __builtin_amdgcn_readfirstlane((uint32_t)(tbase >> 32));
+        const int64_t end = n - p0 < kTonePiece ? n : p0 + kTonePiece;
+        rsrc_tail = __builtin_amdgcn_make_buffer_rsrc((void *)(((uint64_t)thi << 32) | tlo), 0, (int)(end - split) * 4,
+                                                      0x00020000);
+    }
 #pragma unroll
     for (int u = 0; u < kToneGroups; ++u) {
         const int64_t f = f0 + (int64_t)u * kToneGroupStride;
@@ -134,15 +162,37 @@ __device__ __forceinline__ void tone_piece(float *__restrict__ out, int64_t n, c
             for (int j = 0; j < 4; ++j) y[j] += __builtin_fma(rows[2 * j], qx, rows[2 * j + 1] * qy);
         }
         if (f < n) {
-            if (PGX_HOT(aligned && f + 4 <= n)) {
+            if (SPLIT && PGX_COLD(straddle)) {
+                const tone_v4u v = {__float_as_uint((float)y[0]), __float_as_uint((float)y[1]),
+                                    __float_as_uint((float)y[2]), __float_as_uint((float)y[3])};
+                if (aligned && f + 4 <= split) {
+                    __builtin_amdgcn_raw_buffer_store_b128(v, rsrc, (tid * 4 + u * kToneGroupStride) * 4, 0,
+                                                           PGX_TONE_STORE_AUX /* sc1 */);
+                } else if (tail_aligned && f >= split && f + 4 <= n) {
+                    __builtin_amdgcn_raw_buffer_store_b128(v, rsrc_tail, (int)(f - split) * 4, 0,
+                                                           PGX_TONE_STORE_AUX /* sc1 */);
+                } else {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const int64_t g = f + j;
+                        if (g < split) out[g] = (float)y[j];
+                        else if (g < n) tail[g - split] = (float)y[j];
+                    }
+                }
+            } else if (PGX_HOT(aligned && f + 4 <= lim)) {
                 const tone_v4u v = {__float_as_uint((float)y[0]), __float_as_uint((float)y[1]),
                                     __float_as_uint((float)y[2]), __float_as_uint((float)y[3])};
                 __builtin_amdgcn_raw_buffer_store_b128(v, rsrc, (tid * 4 + u * kToneGroupStride) * 4, 0,
                                                        PGX_TONE_STORE_AUX /* sc1 */);
             } else {
 #pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    if (f + j < n) out[f + j] = (float)y[j];
+                for (int j = 0; j < 4; ++j) {
+                    if (SPLIT) {
+                        if (f + j < lim) dst[f - p0 + j] = (float)y[j];
+                    } else {
+                        if (f + j < n) out[f + j] = (float)y[j];
+                    }
+                }
             }
         }
         if (u + 1 < kToneGroups) {
@@ -153,13 +203,15 @@ __device__ __forceinline__ void tone_piece(float *__restrict__ out, int64_t n, c
     }
 }
 
-// Eight waves per SIMD (<= 64 VGPRs): nothing but the stores is waited for, and the more waves the more of them in flight
-__global__ void __launch_bounds__(kToneBlock, 8)
-k_biquad_tone(float *__restrict__ out, int64_t n, const double *__restrict__ tables, double *state,
-              double *state_backup, ToneArgs a) {
+template <bool SPLIT>
+__device__ __forceinline__ void tone_block(float *__restrict__ out, int64_t n, const double *__restrict__ tables,
+                                           double *state, double *state_backup, const ToneArgs &a,
+                                           float *__restrict__ tail, int64_t split) {
     const bool aligned = ((uintptr_t)out & 15) == 0;
+    // a 16-byte store into the tail: the split on a group's edge and the tail's base on a 16-byte one
+    const bool tail_aligned = SPLIT && ((uintptr_t)tail & 15) == 0 && (split & 3) == 0;
     if (blockIdx.x != 0) {
-        tone_piece<false>(out, n, tables, a, (int64_t)blockIdx.x, aligned, 0.0, 0.0);
+        tone_piece<false, SPLIT>(out, n, tables, a, (int64_t)blockIdx.x, aligned, 0.0, 0.0, tail, split, tail_aligned);
         return;
     }
     // workgroup 0: every thread reads the carried state before thread 0 replaces it
@@ -183,7 +235,22 @@ k_biquad_tone(float *__restrict__ out, int64_t n, const double *__restrict__ tab
     }
     // one piece, not a loop over ceil(settle / 4096) of them: around a loop the compiler keeps the sincos' constants in
     // registers and 84 - 108 bytes per lane of the whole kernel went to scratch (pgx_biquad_tone_supported: settle <= 4096)
-    tone_piece<true>(out, n, tables, a, 0, aligned, sx - zx, sy - zy);
+    tone_piece<true, SPLIT>(out, n, tables, a, 0, aligned, sx - zx, sy - zy, tail, split, tail_aligned);
+}
+
+// Eight waves per SIMD (<= 64 VGPRs): nothing but the stores is waited for, and the more waves the more of them in flight
+__global__ void __launch_bounds__(kToneBlock, 8)
+k_biquad_tone(float *__restrict__ out, int64_t n, const double *__restrict__ tables, double *state,
+              double *state_backup, ToneArgs a) {
+    tone_block<false>(out, n, tables, state, state_backup, a, nullptr, n);
+}
+
+// ... with frames [split, n) stored to tail[0 ...] (pgx_biquad_tone_window_split): an instantiation of its own, so that
+// the unsplit kernel keeps its registers and its instructions
+__global__ void __launch_bounds__(kToneBlock, 8)
+k_biquad_tone_split(float *__restrict__ out, float *__restrict__ tail, int64_t split, int64_t n,
+                    const double *__restrict__ tables, double *state, double *state_backup, ToneArgs a) {
+    tone_block<true>(out, n, tables, state, state_backup, a, tail, split);
 }
 
 // |H(e^jd)|, arg H and sum|h| of one coefficient set, kept for the set asked about last: a stream of windows asks for
@@ -244,16 +311,20 @@ static bool tone_supported(int64_t n, int64_t settle, double w, double sr, doubl
     return std::isfinite(f.gain) && std::isfinite(f.l1) && f.l1 <= kToneNoiseRatio * f.gain;
 }
 
-// Frames per look-ahead window of a stream of these windows.  The kernel is bound by its stores, and a stream has two
-// windows live (their buffers alternate): while both stay in the 256 MiB memory-side cache a window is overwritten with
-// its lines still on the die and is stored at the cache's rate (0.53 us per M frames + 1.8 us) instead of HBM's (0.67).
-// The sweep of profiles/c2_resident_windows.md, bench.py at 1 M-frame steps, Msamples/s of the parent's 1 449 000 -
-// 1 521 000 (134 M-frame windows): 24 M 1 309 000 - 1 323 000, 30 M 1 470 000 - 1 537 000, 32 M 1 497 000 - 1 586 000 (one
-// run 1 337 000), 34 M 1 570 000 - 1 629 000 (one 1 491 000), 36 M 1 585 000 - 1 679 000, 38 M 1 573 000 - 1 656 000, 40 M
-// 1 572 000 - 1 641 000, 44 M 1 541 000 - 1 654 000, 48 M 1 381 000 - 1 479 000.  Below 36 M the host bounds the stream (an
-// opening costs it 11 - 12 us, a served step 0.28), at 36 M the traced kernel still runs at the cache's rate (21.2 us,
-// 0.59 us per M frames) and host and device are level; from 40 M on the device falls back towards HBM's rate.
-constexpr int64_t kToneWindowFrames = 36000000;
+// Frames per look-ahead window of a stream of these windows.  The kernel is bound by its stores.  A stream has one big
+// buffer live: a window's last block is stored to a buffer of its own (k_biquad_tone_split), so a caller that keeps the
+// last snippet it pulled keeps those 4 MB and the window's buffer returns to the pool when the window is used up; the
+// next window gets the same address and is stored over lines that are still in the 256 MiB memory-side cache.  Into one
+// rewritten buffer the kernel costs 0.552 - 0.576 us per M frames from 36 M to 67 M frames (into two in turn 0.587 at
+// 36 M, 0.60 at 40 M, 0.67 from 48 M on: tools/c2_resident_probe.py single), and the larger the window the less of the
+// host's cost of an opening falls on a step.  The sweep of profiles/c2_single_window.md, bench.py at 1 M-frame steps,
+// Msamples/s, three runs per size alternated with the parent's 1 536 000 - 1 667 000 (36 M-frame windows, two buffers):
+// 36 M 1 503 000 - 1 526 000 (the host bounds it: an opening costs more than the parent's), 44 M 1 676 000 - 1 721 000,
+// 48 M 1 739 000 - 1 781 000, 52 M 1 772 000 - 1 795 000, 56 M 1 790 000 - 1 813 000, 60 M 1 788 000 - 1 803 000,
+// 64 M 1 804 000 - 1 821 000, 67 M 1 774 000 - 1 811 000.  64 M has the highest minimum; the probe's 64 M-frame launch is
+// also its cheapest per frame (35.3 us, 0.552 us per M frames).  With PGX_TONE_SPLIT_TAIL=0 two buffers alternate again,
+// and 36 M is the size to ask for (PGX_TONE_WINDOW_FRAMES).
+constexpr int64_t kToneWindowFrames = 64000000;
 
 static int64_t tone_window_frames_env() {
     const char *e = getenv("PGX_TONE_WINDOW_FRAMES");      // 0: no preference
@@ -318,9 +389,12 @@ static bool tone_make_plan(TonePlan &p, double sample_rate, double w, double amp
     return true;
 }
 
+// tail_frames > 0: frames [n - tail_frames, n) go to out_tail[0 ...]
 static int tone_launch(const TonePlan &p, float *out, int64_t start, int64_t n, double *state, double *state_backup,
-                       const char *who) {
-    PGX_CHECK_ARG(out && state, std::string(who) + ": bad argument");
+                       const char *who, float *out_tail = nullptr, int64_t tail_frames = 0) {
+    PGX_CHECK_ARG(tail_frames >= 0 && tail_frames <= n, std::string(who) + ": tail_frames outside [0, n]");
+    PGX_CHECK_ARG(tail_frames == 0 || out_tail, std::string(who) + ": tail frames and no out_tail");
+    PGX_CHECK_ARG((out || tail_frames == n) && state, std::string(who) + ": bad argument");
     PGX_CHECK_ARG(pgx_biquad_table_doubles() == (size_t)kTabDoubles, std::string(who) + ": table layout changed");
     // what of pgx_biquad_tone_supported depends on the block: n >= 2 settle_frames and the phase advance over it
     PGX_CHECK_ARG(n >= 2 * p.a.settle && p.w_abs * ((double)n / p.a.sr) < pgx::kSinFastRange,
@@ -332,6 +406,12 @@ static int tone_launch(const TonePlan &p, float *out, int64_t start, int64_t n, 
     a.start = start;
     const int64_t pieces = pgx::ceil_div(n, (int64_t)kTonePiece);
     PGX_CHECK_ARG(pieces <= 0x7fffffff, std::string(who) + ": block too long");
+    if (tail_frames > 0) {
+        hipLaunchKernelGGL(k_biquad_tone_split, dim3((unsigned)pieces), dim3(kToneBlock), 0, pgx::stream(), out, out_tail,
+                           n - tail_frames, n, p.tables, state, state_backup, a);
+        PGX_LAUNCH_CHECK("k_biquad_tone_split");
+        return PGX_OK;
+    }
     hipLaunchKernelGGL(k_biquad_tone, dim3((unsigned)pieces), dim3(kToneBlock), 0, pgx::stream(), out, n, p.tables, state,
                        state_backup, a);
     PGX_LAUNCH_CHECK("k_biquad_tone");
@@ -381,6 +461,25 @@ int pgx_biquad_tone_window(const void *plan, float *out, int64_t start, int64_t 
     if (n <= 0) return PGX_OK;
     PGX_CHECK_ARG(plan, "pgx_biquad_tone_window: no plan");
     return tone_launch(*static_cast<const TonePlan *>(plan), out, start, n, state, state_backup, "pgx_biquad_tone_window");
+}
+
+int pgx_biquad_tone_window_split(const void *plan, float *out, float *out_tail, int64_t tail_frames, int64_t start,
+                                 int64_t n, double *state, double *state_backup) {
+    PGX_REQUIRE_INIT();
+    PGX_CHECK_ARG(tail_frames >= 0 && (n <= 0 || tail_frames <= n), "pgx_biquad_tone_window_split: tail_frames outside [0, n]");
+    PGX_CHECK_ARG(tail_frames == 0 || out_tail, "pgx_biquad_tone_window_split: tail frames and no out_tail");
+    if (n <= 0) return PGX_OK;
+    PGX_CHECK_ARG(plan, "pgx_biquad_tone_window_split: no plan");
+    return tone_launch(*static_cast<const TonePlan *>(plan), out, start, n, state, state_backup,
+                       "pgx_biquad_tone_window_split", out_tail, tail_frames);
+}
+
+int pgx_biquad_tone_split_tail(void) {
+    static const int wanted = []() {
+        const char *e = getenv("PGX_TONE_SPLIT_TAIL");
+        return (e && e[0] == '0' && e[1] == 0) ? 0 : 1;
+    }();
+    return wanted;
 }
 
 int pgx_biquad_tone(float *out, int64_t start, int64_t n, double sample_rate, double w, double amp, double phase0,

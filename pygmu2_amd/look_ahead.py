@@ -47,7 +47,7 @@ AHEAD_FRAMES_SMALL_GRAPH = int(os.environ.get("PGX_LOOK_AHEAD_FRAMES_SMALL", str
                             # and warm-up halves per frame, a quarter of the window openings).  That was measured while the
                             # window kernel was compute-bound.  A window root whose kernel is bound by its stores says so
                             # itself (`_look_ahead_frames()`, window_blocks below): BiquadPE(SinePE)'s closed-form windows
-                            # are kept small enough for two of them to stay in the memory-side cache.
+                            # are kept small enough to stay in the memory-side cache.
 _FRAMES_EXPLICIT = "PGX_LOOK_AHEAD_FRAMES" in os.environ
 
 
@@ -221,7 +221,11 @@ def _note_window_failure(pe, exc) -> None:
 
 # ------------------------------------------------------------------------------------ windows
 class _Window:
-    __slots__ = ("first", "end", "buf", "served", "snap", "nodes", "block")     # block: 0, or the only block size served
+    # block: 0, or the only block size served.  tail: None, or the buffer that holds the frames [split, end) -- a window
+    # root that renders its window itself (`_render_window`) may put the last caller-sized block there, so that a caller
+    # who keeps the last snippet it pulled keeps that small buffer alive and not `buf`; split == end without one (and is
+    # only looked at with one).
+    __slots__ = ("first", "end", "buf", "served", "snap", "nodes", "block", "tail", "split")
 
 
 def render(pe, start: int, duration: int):
@@ -240,11 +244,16 @@ def render(pe, start: int, duration: int):
         return None
     if win is not None:
         if start == win.served and start + duration <= win.end and (not win.block or duration == win.block):
-            win.served = start + duration
-            d["_la_last"] = win.served                # the pull after the window's last block continues the stream
-            from .snippet import Snippet
-            return Snippet.window_rows(start, win.buf, start - win.first, duration)
+            # rows of `buf` or rows of the tail; a pull that lies across the two is one the window cannot serve
+            rows = ((win.buf, start - win.first) if getattr(win, "tail", None) is None or start + duration <= win.split
+                    else (win.tail, start - win.split) if start >= win.split else None)
+            if rows is not None:
+                win.served = start + duration
+                d["_la_last"] = win.served            # the pull after the window's last block continues the stream
+                from .snippet import Snippet
+                return Snippet.window_rows(start, rows[0], rows[1], duration)
         settle(pe)
+        win = rows = None                             # the buffers go back to the pool before the next window asks for one
     if duration > SMALL_BLOCK or not capable(pe):
         return None
     sequential = d.get("_la_last") == start
@@ -272,8 +281,17 @@ def render(pe, start: int, duration: int):
     grow = d.get("_la_grow", FIRST_WINDOW_BLOCKS)
     hint = getattr(pe, "_look_ahead_frames", None)
     blocks = window_blocks(grow, duration, len(nodes), hint() if hint is not None else None)
+    tail = None
     try:
-        big = pe._render(start, duration * blocks)
+        # a window root may render its window itself and hand the last block back in a buffer of its own:
+        # _render_window(start, duration, blocks) -> (Snippet of the first blocks - 1 blocks, DeviceBuffer of the last),
+        # or None: rendered as usual
+        own = getattr(pe, "_render_window", None)
+        parts = own(start, duration, blocks) if own is not None else None
+        if parts is None:
+            big = pe._render(start, duration * blocks)
+        else:
+            big, tail = parts
     except BaseException as exc:
         # a render `blocks` times longer can fail where the block itself would not (HBM for the intermediates,
         # a kernel's size limit, a PE that declines the window): every state goes back to the snapshot, this PE stops
@@ -311,7 +329,8 @@ def render(pe, start: int, duration: int):
         finally:
             _tls.busy = False
     win = _Window()
-    win.first, win.end, win.buf = start, start + big.duration, big.dev
+    win.first, win.split, win.buf, win.tail = start, start + big.duration, big.dev, tail
+    win.end = win.split + (tail.shape[0] if tail is not None else 0)
     win.served, win.snap, win.nodes, win.block = start + duration, snap, nodes, block
     d["_la_win"] = win
     for n in d["_la_below"]:

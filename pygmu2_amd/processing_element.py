@@ -79,8 +79,13 @@ class ProcessingElement(ABC):
             if win is not None:
                 end = start + duration
                 if start == win.served and end <= win.end and (not win.block or duration == win.block):
-                    win.served = d["_la_last"] = end
-                    return Snippet.window_rows(start, win.buf, start - win.first, duration)
+                    tail = getattr(win, "tail", None)      # the window's last block in a buffer of its own (look_ahead.py)
+                    if tail is None or end <= win.split:
+                        win.served = d["_la_last"] = end
+                        return Snippet.window_rows(start, win.buf, start - win.first, duration)
+                    if start >= win.split:
+                        win.served = d["_la_last"] = end
+                        return Snippet.window_rows(start, tail, start - win.split, duration)
             else:
                 win = d.get("_ra_win")                   # read-ahead window of a pure sub-graph: (first, end, buffer[, period])
                 if (win is not None and win[0] <= start and start + duration <= win[1]
