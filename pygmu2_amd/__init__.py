@@ -8,7 +8,7 @@ AdsrGatedPE, AdsrTriggeredPE, PeriodicGate, PeriodicTrigger, ConstantPE, ArrayPE
 DiracPE, IdentityPE, CachePE, CropPE, SVFilterPE, EnvelopePE, TransformPE, DelayPE, PiecewisePE,
 TriggerRestartPE, ReverbPE, WavWriterPE, WavReaderPE, KarplusStrongPE, AnalogOscPE, WavetablePE, TimeWarpPE,
 SampleHoldPE, TrackHoldPE, SlewLimiterPE, FunctionGenPE, NoisePE, TralfamPE, SlicePE, SetExtentPE, SequencePE,
-ReversePitchEchoPE, PortamentoPE, ControlPE
+ReversePitchEchoPE, PortamentoPE, ControlPE, MeltysynthPE
 (+ render_to_file, rho_for_decay_db, pitch_to_freq and the other unit conversions).  Snippet payloads live in HBM; all DSP runs in
 hand-written HIP kernels for gfx950 behind the C ABI of include/pygmu_hip.h.
 """
@@ -109,6 +109,12 @@ from .reverse_pitch_echo_pe import ReversePitchEchoPE
 # tests/test_stream_control_pe.py the control.
 from .portamento_pe import PortamentoPE
 from .control_pe import ControlPE
+# MeltysynthPE and the `soundfont` package (the SF2 reader and the synthesizer's control plane): the same arrangement
+# (pg.MeltysynthPE and pg.soundfont work, neither is in __all__): the fuzz census of tests/test_oracle_fuzz_golden.py
+# needs an evaluator under oracle/ for every name listed there; tests/test_soundfont_host.py holds the reader and the
+# control plane, tests/test_zzz_gpu_soundfont.py the device, to fixtures of the reference.
+from . import soundfont
+from .meltysynth_pe import MeltysynthPE
 from .utils import render_to_file
 from . import device, diagnostics
 

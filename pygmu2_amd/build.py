@@ -44,6 +44,7 @@ SOURCES = [
     "pgx_tuning.hip",
     "pgx_restart.hip",
     "pgx_reverse_echo.hip",
+    "pgx_soundfont.hip",
 ]
 
 # -ffp-contract=off: the parity contract is "same float64 operation order as the reference's
